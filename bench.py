@@ -16,10 +16,17 @@ Multi-rank: launched by torch.distributed.run with one rank per GPU
 (RCCL); total work fixed (BASELINE quotes 1e9 pts at every GPU count)
 => scaling = "strong".
 
-Output: ONE JSON line from rank 0, with `roofline` (paint-kernel
-achieved HBM GB/s from HIP events vs the 8 TB/s peak) and
-`cpu_baseline` (the numpy oracle timed on this box's host cores on a
-bounded sample).
+A plain run does only what the headline figure needs: generate the
+catalog, warm up, time `--steps` steps, optionally write the last timed
+step's result (`--dump-outputs DIR`) and print ONE JSON line from rank 0
+(`value` = particles/s, `ms_per_step` = wall milliseconds per timed
+step).  Generation is seeded, so the same arguments give the same
+inputs on every run and two builds can be compared output for output.
+
+`--full` adds everything else to that line: `roofline` (paint-kernel
+achieved HBM GB/s from HIP events recorded during the timed steps vs
+the 8 TB/s peak, plus one untimed pure-paint launch) and `cpu_baseline`
+(the numpy oracle timed on the host cores on a bounded sample).
 """
 import argparse
 import json
@@ -304,6 +311,34 @@ def gen_lognormal(n_total, nmesh, box, rank, ws, seed, bias=2.0,
     return pos
 
 
+# ---- result dump --------------------------------------------------------
+
+def dump_outputs(result, outdir):
+    """Write what a caller of FFTPower receives — every variable of
+    `result.power` (and `result.poles`, when computed) plus the
+    normalization attrs — as float64 `<outdir>/<name>.npy`; complex
+    variables are split into `_real` / `_imag`.  A few KB in all."""
+    os.makedirs(outdir, exist_ok=True)
+
+    def save(name, arr):
+        arr = numpy.asarray(arr)
+        if numpy.iscomplexobj(arr):
+            save(name + '_real', arr.real)
+            save(name + '_imag', arr.imag)
+            return
+        numpy.save(os.path.join(outdir, name + '.npy'),
+                   numpy.ascontiguousarray(arr, dtype='f8'))
+
+    for label in ('power', 'poles'):
+        stat = getattr(result, label)
+        if stat is None:
+            continue
+        for var in stat.variables:
+            save('%s_%s' % (label, var), stat[var])
+    for key in ('shotnoise', 'N1', 'N2'):
+        save('attrs_' + key, result.attrs[key])
+
+
 # ---- main ---------------------------------------------------------------
 
 def main():
@@ -318,11 +353,21 @@ def main():
                     choices=sorted(WORKLOADS))
     ap.add_argument('--particles', type=int, default=None)
     ap.add_argument('--nmesh', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also report the paint roofline (HIP events on '
+                         'the timed steps + one pure-paint launch) and '
+                         'the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the result of the last timed step as '
+                         'DIR/<name>.npy (float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baseline')
     ap.add_argument('--traffic-bytes', type=float, default=None,
                     help='measured HBM bytes per paint launch from '
                          'rocprofv3 --pmc (see profiles/)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     import torch
     ws = int(os.environ.get('WORLD_SIZE', '1'))
@@ -404,7 +449,8 @@ def main():
         torch.cuda.synchronize()
         comm.barrier()
 
-        profiling.enable()
+        if args.full:
+            profiling.enable()
         t0 = time.time()
         for _ in range(args.steps):
             result = step()
@@ -413,14 +459,17 @@ def main():
         elapsed = time.time() - t0
     elapsed = comm.allreduce(elapsed, op='max')
 
-    prof = profiling.summary()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(result, args.dump_outputs)
+
+    prof = profiling.summary() if args.full else {}
 
     # one untimed pure-paint launch (real-mesh gather, no fused z-FFT)
     # so the bench line can quote BOTH fractions (r01 verdict item 6):
     # the fused kernel contains FFT work its byte model doesn't count
     pure_paint = None
     gather0 = paint_is_gather(nmesh, len(pos))
-    if rank == 0 and ws == 1 and gather0:
+    if args.full and rank == 0 and ws == 1 and gather0:
         profiling.reset()
         with set_options(paint_chunk_size=1 << 30):
             # to_real_field directly: compute('real') on a compensated
@@ -467,7 +516,7 @@ def main():
         traffic = PMC_TRAFFIC_BYTES.get((args.workload, gather))
 
     cpu_baseline = None
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline:
         cpu_baseline = run_cpu_baseline(cfg)
 
     if rank == 0:
@@ -525,6 +574,9 @@ def main():
             'peak_hbm_gb': round(
                 torch.cuda.max_memory_allocated() / 1e9, 2),
         }
+        if not args.full:
+            # a plain run recorded no events and ran no baseline
+            del out['roofline'], out['cpu_baseline']
         print(json.dumps(out), flush=True)
 
     if ws > 1:
