@@ -117,7 +117,11 @@ int nbk_paint_sorted_f64(const double* pos, const double* mass, int64_t n,
  * contiguous range per (x-plane pair, y-group); the tile geometry is
  * pinned to (1 plane x 1<<pair_gs rows) and the deposit masks drop the
  * duplicated out-of-tile copies.  pair_gs = -1: per-row table from
- * nbk_bucket_fine_f64. */
+ * nbk_bucket_fine_f64.  Both table modes serve every window and shift
+ * (the sort's [dlo, dhi] must cover the window's rows at that shift),
+ * and any n0: on a mesh with fewer x-planes than a tile's source span
+ * the plane walk stops after n0 planes, so no source plane and no pair
+ * bucket is read twice. */
 int nbk_paint_gather_f64(const double* pos, const double* mass, int64_t n,
                          const int64_t nmesh[3], const double box[3],
                          int window, double shift, const int* rowtab,
@@ -175,8 +179,8 @@ int nbk_bucket_scatter_f64(const double* pos_aos, const double* mass,
  *     scrambled_flag (may be NULL);
  *   - nbk_scan_matrix_i32: device scan of `mat` -> per-chunk cursor
  *     seeds `bases` (chunk-major) and bucket edges `bucket_bases`
- *     (nbuckets+1, exclusive; [nbuckets] = n).  colsum_tmp is nbuckets
- *     ints of scratch;
+ *     (nbuckets+1, exclusive; [nbuckets] = n).  colsum_tmp is
+ *     9 * nbuckets ints of scratch (8 segment partials + column sums);
  *   - nbk_xsort_scatter_f64 (pass C): re-reads each chunk, places SoA
  *     planes (x[n] y[n] z[n] into pos_out) from LDS cursors seeded
  *     with `bases` (deterministic — no global atomics);

@@ -410,7 +410,16 @@ __global__ void kpaint_gather(const double* __restrict__ px,
     // row intervals (wrapped) whose particles can deposit into the tile
     const int64_t rspan = (int64_t)RG + (xhi - xlo);
     int64_t prev_pair = -1;
-    for (int dp = xlo; dp <= P - 1 + xhi; dp++) {
+    // The walk covers P + (xhi - xlo) consecutive source planes.  On a
+    // mesh thinner than that it would wrap past its own start and
+    // deposit the revisited planes twice: stop after n0 planes (every
+    // plane once) — the x analogue of the rspan >= n1 case below.
+    // Wave-uniform; a no-op whenever n0 >= P + span.
+    const int dp_hi = ((int64_t)P + (xhi - xlo) > n0)
+        ? (int)(xlo + n0 - 1) : P - 1 + xhi;
+    const int64_t npairs = n0 >> 1;       // pair mode: distinct buckets
+    int64_t pairs_read = 0;
+    for (int dp = xlo; dp <= dp_hi; dp++) {
         const int64_t p = wrap_idx(px0 + dp, n0);
         int64_t ivals[2][2];
         int niv;
@@ -419,10 +428,15 @@ __global__ void kpaint_gather(const double* __restrict__ px,
             // copy of every stencil-relevant particle in this tile's
             // own (pair, group) bucket — one contiguous range, no
             // halo-row lookups.  Consecutive source planes share a
-            // pair: read each pair once.
+            // pair: read each pair once.  (prev_pair only catches
+            // neighbours: a walk over all n0 planes that starts on an
+            // odd plane ends in its first pair again — the count of
+            // distinct pairs stops it there.)
             const int64_t q = p >> 1;
             if (q == prev_pair) continue;
+            if (pairs_read == npairs) break;
             prev_pair = q;
+            pairs_read++;
             const int64_t ng = n1 >> gs;
             const int64_t bidx = q * ng + (r0 >> gs);
             ivals[0][0] = rowtab[bidx];

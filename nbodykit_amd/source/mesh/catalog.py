@@ -102,9 +102,12 @@ _PAIR_GHOST = {
     # stencil at BOTH interlacing shifts when interlaced (the one sorted
     # array feeds both paints); Dlo = dmin, Dhi = dmax + support - 1
     # from the paint launchers' (dmin, dmax) source-span logic
-    # (csrc/nbk_paint.hip).  Only the CIC rows are exercised today (the
-    # pair sort is gated to CIC non-interlaced); the others are kept
-    # correct for any future widening of that gate.
+    # (csrc/nbk_paint.hip).  The driver only takes the (cic, False) row
+    # (the pair sort is gated to CIC non-interlaced for speed); every
+    # row is pinned against the oracle stencil in
+    # tests/test_sort_tables_cpu.py and painted through the pair-bucket
+    # gather at the C ABI in tests/test_gpu_sort_kernels.py, so the gate
+    # can widen without touching them.
     ('cic', False): (0, 1), ('cic', True): (0, 2),
     ('tsc', False): (-1, 2), ('tsc', True): (-1, 2),
     ('pcs', False): (-1, 2), ('pcs', True): (-1, 3),
