@@ -45,11 +45,48 @@ __device__ __forceinline__ cdouble cscale(cdouble a, double s) {
 // always a single AND — the general int64 modulo is a ~30-op sequence
 // and the paint/count kernels issue up to 14 wraps per particle.  The
 // n is wave-uniform, so the check is scalar and predicted.
+// wrap_generic is the any-n modulo alone, for callers that took the
+// power-of-two decision themselves, once per kernel (the gather paint's
+// particle loop is instantiated for both answers).
+__device__ __forceinline__ int64_t wrap_generic(int64_t i, int64_t n) {
+    i %= n;
+    return i < 0 ? i + n : i;
+}
 __device__ __forceinline__ int64_t wrap_idx(int64_t i, int64_t n) {
     if (__builtin_expect((n & (n - 1)) == 0, 1))
         return i & (n - 1);
-    i %= n;
-    return i < 0 ? i + n : i;
+    return wrap_generic(i, n);
+}
+
+// Hardware-predicated f64 loads for software-pipelined loops.  A raw
+// buffer descriptor over [base, base + bytes) makes the memory unit
+// itself drop every lane whose byte offset falls outside: the lane
+// reads nothing and gets 0.  Unlike `ok ? p[i] : 0.0` — which hipcc
+// lowers to a skip branch around each load, after which it can no
+// longer count the loads in flight and waits vmcnt(0) — the load stays
+// one unconditional instruction, so a batch of them is waited for with
+// a counted s_waitcnt vmcnt(N) while the next batch is outstanding.
+// base and bytes must be wave-uniform (the readfirstlanes make that
+// provable to the compiler, so the descriptor lives in SGPRs).
+typedef unsigned int nbk_u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t
+nbk_buffer_rsrc(const double* base, uint32_t bytes) {
+    const uint64_t a = (uint64_t)base;
+    const uint64_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
+    const uint64_t hi =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((hi << 32) | lo), 0,
+        __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+}
+
+// the double at byte offset `off` of the descriptor's range, 0.0 beyond
+__device__ __forceinline__ double
+nbk_buffer_load_f64(__amdgpu_buffer_rsrc_t rsrc, uint32_t off) {
+    const nbk_u32x2 v =
+        __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off, 0, 0);
+    return __hiloint2double((int)v.y, (int)v.x);
 }
 
 // signed frequency of global index g on an axis of size n (numpy

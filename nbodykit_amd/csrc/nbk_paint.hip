@@ -25,6 +25,7 @@
 // (source/mesh/catalog.py:453-594; Jing 2005 eq. 18, p = 2/3/4);
 // a particle exactly on a grid point deposits its full mass there.
 #include "nbk_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -407,8 +408,30 @@ __global__ void kpaint_gather(const double* __restrict__ px,
     for (int64_t w = t; w < win; w += T) tile[w] = 0.0;
     __syncthreads();
 
+    // The particle loop is software-pipelined through registers: each
+    // thread stages a batch of U particles (3-4 loads each, issued back
+    // to back) and the loads of batch k+1 are issued BEFORE batch k's
+    // weights, masks and ds_add_f64, so the HBM read stream and the LDS
+    // atomic pipe work at the same time — one block per CU is resident
+    // (the tile fills the LDS), so no other block would cover the wait.
+    // The two batches ping-pong (no register copies) and the pipeline
+    // runs across the tile's ranges: it fills once per tile, not once
+    // per range.  A batch never spans two ranges; every load is
+    // predicated on its own range's end.
+    constexpr int U = (WINDOW == NBK_WINDOW_CIC) ? 4 : 2;
+    struct Batch {
+        double x[U], y[U], z[U], m[U];   // m only with a mass array
+        uint32_t cnt;                 // slot u of thread t holds a
+                                      // particle iff u*T + t < cnt
+    };
+
     // row intervals (wrapped) whose particles can deposit into the tile
     const int64_t rspan = (int64_t)RG + (xhi - xlo);
+    // row-table mode: the reachable rows [ra, rb] (the same for every
+    // source plane); ra > rb = the interval wraps and is read as
+    // [ra, n1) then [0, rb]
+    const int64_t ra = wrap_idx(r0 + xlo, n1);
+    const int64_t rb = wrap_idx(r0 + RG - 1 + xhi, n1);
     int64_t prev_pair = -1;
     // The walk covers P + (xhi - xlo) consecutive source planes.  On a
     // mesh thinner than that it would wrap past its own start and
@@ -419,50 +442,120 @@ __global__ void kpaint_gather(const double* __restrict__ px,
         ? (int)(xlo + n0 - 1) : P - 1 + xhi;
     const int64_t npairs = n0 >> 1;       // pair mode: distinct buckets
     int64_t pairs_read = 0;
-    for (int dp = xlo; dp <= dp_hi; dp++) {
-        const int64_t p = wrap_idx(px0 + dp, n0);
-        int64_t ivals[2][2];
-        int niv;
-        if (gs >= 0) {
-            // PAIR-BUCKET mode: the duplicating sort already placed a
-            // copy of every stencil-relevant particle in this tile's
-            // own (pair, group) bucket — one contiguous range, no
-            // halo-row lookups.  Consecutive source planes share a
-            // pair: read each pair once.  (prev_pair only catches
-            // neighbours: a walk over all n0 planes that starts on an
-            // odd plane ends in its first pair again — the count of
-            // distinct pairs stops it there.)
-            const int64_t q = p >> 1;
-            if (q == prev_pair) continue;
-            if (pairs_read == npairs) break;
-            prev_pair = q;
-            pairs_read++;
-            const int64_t ng = n1 >> gs;
-            const int64_t bidx = q * ng + (r0 >> gs);
-            ivals[0][0] = rowtab[bidx];
-            ivals[0][1] = rowtab[bidx + 1];
-            niv = 1;
-        } else if (rspan >= n1) {
-            ivals[0][0] = 0; ivals[0][1] = n1 - 1; niv = 1;
-        } else {
-            const int64_t a = wrap_idx(r0 + xlo, n1);
-            const int64_t b = wrap_idx(r0 + RG - 1 + xhi, n1);
-            if (a <= b) { ivals[0][0] = a; ivals[0][1] = b; niv = 1; }
-            else {
-                ivals[0][0] = a; ivals[0][1] = n1 - 1;
-                ivals[1][0] = 0; ivals[1][1] = b; niv = 2;
-            }
+    int dp = xlo;
+    int64_t tail_p = -1;      // plane whose wrapped second interval waits
+    // the next range [i0, i1) of sorted particles this tile reads;
+    // wave-uniform (scalar table loads), false when the walk is over
+    auto next_range = [&](uint32_t& i0, uint32_t& i1) -> bool {
+        if (tail_p >= 0) {
+            i0 = rowtab[tail_p * n1];
+            i1 = rowtab[tail_p * n1 + rb + 1];
+            tail_p = -1;
+            return true;
         }
-        for (int v = 0; v < niv; v++) {
-            const int64_t i0 = (gs >= 0) ? ivals[v][0]
-                : rowtab[p * n1 + ivals[v][0]];
-            const int64_t i1 = (gs >= 0) ? ivals[v][1]
-                : rowtab[p * n1 + ivals[v][1] + 1];
-            for (int64_t i = i0 + t; i < i1; i += T) {
-                const double u0 = px[i] * invH0 + shift;
-                const double u1 = py[i] * invH1 + shift;
-                const double u2 = pz[i] * invH2 + shift;
-                const double m = mass ? mass[i] : 1.0;
+        while (dp <= dp_hi) {
+            const int64_t p = wrap_idx(px0 + dp, n0);
+            dp++;
+            if (gs >= 0) {
+                // PAIR-BUCKET mode: the duplicating sort already placed
+                // a copy of every stencil-relevant particle in this
+                // tile's own (pair, group) bucket — one contiguous
+                // range, no halo-row lookups.  Consecutive source
+                // planes share a pair: read each pair once.  (prev_pair
+                // only catches neighbours: a walk over all n0 planes
+                // that starts on an odd plane ends in its first pair
+                // again — the count of distinct pairs stops it there.)
+                const int64_t q = p >> 1;
+                if (q == prev_pair) continue;
+                if (pairs_read == npairs) { dp = dp_hi + 1; break; }
+                prev_pair = q;
+                pairs_read++;
+                const int64_t bidx = q * (n1 >> gs) + (r0 >> gs);
+                i0 = rowtab[bidx];
+                i1 = rowtab[bidx + 1];
+            } else if (rspan >= n1) {
+                i0 = rowtab[p * n1];
+                i1 = rowtab[p * n1 + n1];
+            } else if (ra <= rb) {
+                i0 = rowtab[p * n1 + ra];
+                i1 = rowtab[p * n1 + rb + 1];
+            } else {
+                i0 = rowtab[p * n1 + ra];
+                i1 = rowtab[p * n1 + n1];
+                tail_p = p;
+            }
+            return true;
+        }
+        return false;
+    };
+
+    // unread part [ri, re) of the current range.  The tables are int32
+    // (so is every index), and 32-bit scalars keep the walk on the
+    // scalar unit: a 64-bit scalar compare is done in vector registers,
+    // and a vector temporary that lands on the destination of a load
+    // in flight makes the compiler wait for it, vmcnt(0).
+    uint32_t ri = 0, re = 0;
+    bool more = true;         // ranges left in the walk
+    // issue the loads of the next non-empty batch; false = no particles
+    // left.  Slot u of thread t holds particle i0 + u*T + t (coalesced
+    // per slot, as the unpipelined loop read them).
+    auto issue = [&](Batch& b, auto mass_tag) -> bool {
+        while (more && ri >= re) more = next_range(ri, re);
+        // After the last batch the same loads are still issued, through
+        // empty descriptors (every lane dropped, no memory traffic): a
+        // path that issued none would make the compiler's count of
+        // loads in flight at the consumer collapse to the minimum over
+        // paths, i.e. wait for the prefetched batch too.
+        if (!more) ri = re = 0;
+        // descriptors over the batch's part of the range only: a slot
+        // at or past the range's end is dropped by the bounds check —
+        // nothing is read beyond `re`, the array may end there
+        const uint32_t left = re - ri, full = (uint32_t)(U * T);
+        b.cnt = left < full ? left : full;
+        const uint32_t bytes = b.cnt * 8u;
+        const __amdgpu_buffer_rsrc_t rx = nbk_buffer_rsrc(px + ri, bytes);
+        const __amdgpu_buffer_rsrc_t ry = nbk_buffer_rsrc(py + ri, bytes);
+        const __amdgpu_buffer_rsrc_t rz = nbk_buffer_rsrc(pz + ri, bytes);
+        #pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t off = (uint32_t)(u * T + t) * 8u;
+            b.x[u] = nbk_buffer_load_f64(rx, off);
+            b.y[u] = nbk_buffer_load_f64(ry, off);
+            b.z[u] = nbk_buffer_load_f64(rz, off);
+        }
+        if constexpr (decltype(mass_tag)::value) {
+            const __amdgpu_buffer_rsrc_t rm =
+                nbk_buffer_rsrc(mass + ri, bytes);
+            #pragma unroll
+            for (int u = 0; u < U; u++)
+                b.m[u] = nbk_buffer_load_f64(
+                    rm, (uint32_t)(u * T + t) * 8u);
+        }
+        ri += full;
+        return more;
+    };
+
+    // The power-of-two test of the index wrap is taken once, around two
+    // instances of the loop (wrap_idx re-tests n on each of its up to
+    // 14 calls per particle); non-power-of-two meshes keep the generic
+    // 64-bit modulo.  So is the test for a mass array: with a uniform
+    // branch between a batch's loads, the two paths issue different
+    // numbers of loads and the counted waits fall to the smaller.
+    const uint32_t um0 = (uint32_t)n0 - 1, um1 = (uint32_t)n1 - 1,
+                   um2 = (uint32_t)n2 - 1, upx0 = (uint32_t)px0,
+                   ur0 = (uint32_t)r0;
+    auto particle_loop = [&](auto pot_tag, auto mass_tag) {
+        constexpr bool POT = decltype(pot_tag)::value;
+        constexpr bool MASS = decltype(mass_tag)::value;
+        // weights, tile masks and LDS deposits of one staged batch
+        auto consume = [&](const Batch& b) {
+            #pragma unroll
+            for (int u = 0; u < U; u++) {
+                if ((uint32_t)(u * T + t) >= b.cnt) continue;
+                const double u0 = b.x[u] * invH0 + shift;
+                const double u1 = b.y[u] * invH1 + shift;
+                const double u2 = b.z[u] * invH2 + shift;
+                const double m = MASS ? b.m[u] : 1.0;
                 if (!(phases & 1)) {
                     // reads-only decomposition mode: keep the loads
                     // observable, skip the deposit work
@@ -473,34 +566,90 @@ __global__ void kpaint_gather(const double* __restrict__ px,
                 int64_t b0, b1, b2;
                 paint_weights<WINDOW, SUP>(u0, u1, u2, w0, w1, w2,
                                            b0, b1, b2);
-                #pragma unroll
-                for (int dx = 0; dx < SUP; dx++) {
-                    int64_t pl;
-                    if (PT == 1) {
-                        if (wrap_idx(b0 + dx, n0) != px0) continue;
-                        pl = 0;
-                    } else {
-                        pl = wrap_idx(b0 + dx, n0) - px0;
-                        if (pl < 0) pl += n0;
-                        if (pl >= P) continue;
+                // tile plane / row / z cell reached at stencil offset d
+                // (plane and row relative to the tile; >= P or >= RG:
+                // outside it).  Power-of-two instance: every n <= 2^31,
+                // the wrap is an AND and only the low 32 bits of the
+                // (exactly converted) base cell matter — unsigned 32-bit
+                // modular arithmetic gives the same cells as the 64-bit
+                // modulo at half the VALU work.
+                using idx_t = std::conditional_t<POT, uint32_t, int64_t>;
+                const uint32_t c0 = (uint32_t)b0, c1 = (uint32_t)b1,
+                               c2 = (uint32_t)b2;
+                auto plane = [&](int d) -> idx_t {
+                    if constexpr (POT) return (c0 + d - upx0) & um0;
+                    else {
+                        const int64_t pl = wrap_generic(b0 + d, n0) - px0;
+                        return pl < 0 ? pl + n0 : pl;
                     }
+                };
+                auto row = [&](int d) -> idx_t {
+                    if constexpr (POT) return (c1 + d - ur0) & um1;
+                    else {
+                        const int64_t ly = wrap_generic(b1 + d, n1) - r0;
+                        return ly < 0 ? ly + n1 : ly;
+                    }
+                };
+                auto zcell = [&](int d) -> idx_t {
+                    if constexpr (POT) return (c2 + d) & um2;
+                    else return wrap_generic(b2 + d, n2);
+                };
+                // the SUP x SUP deposits of x-weight wx into tile plane pl
+                auto deposit_plane = [&](idx_t pl, double wx) {
                     #pragma unroll
                     for (int dy = 0; dy < SUP; dy++) {
-                        int64_t ly = wrap_idx(b1 + dy, n1) - r0;
-                        if (ly < 0) ly += n1;
-                        if (ly >= RG) continue;
-                        const double wxy = w0[dx] * w1[dy] * m;
+                        const idx_t ly = row(dy);
+                        if (ly >= (idx_t)RG) continue;
+                        const double wxy = wx * w1[dy] * m;
                         #pragma unroll
-                        for (int dz = 0; dz < SUP; dz++) {
-                            const int64_t gz = wrap_idx(b2 + dz, n2);
+                        for (int dz = 0; dz < SUP; dz++)
                             unsafeAtomicAdd(
-                                &tile[(pl * RG + ly) * sp + gz],
+                                &tile[(pl * (idx_t)RG + ly) * (idx_t)sp
+                                      + zcell(dz)],
                                 wxy * w2[dz]);
-                        }
+                    }
+                };
+                if (PT == 1) {
+                    // single-plane tile: every x offset that hits it
+                    // deposits into the same cells, so their weights
+                    // are summed first and the y-z stencil is issued
+                    // once, not once per x offset (each copy would run
+                    // with most lanes masked off: a wave's particles
+                    // mix the pair's planes).  On a mesh of at least
+                    // SUP planes at most one offset hits and wx is that
+                    // offset's weight itself.
+                    double wx = 0.0;
+                    bool hit = false;
+                    #pragma unroll
+                    for (int dx = 0; dx < SUP; dx++)
+                        if (plane(dx) == 0) { wx += w0[dx]; hit = true; }
+                    if (hit) deposit_plane(0, wx);
+                } else {
+                    #pragma unroll
+                    for (int dx = 0; dx < SUP; dx++) {
+                        const idx_t pl = plane(dx);
+                        if (pl < (idx_t)P) deposit_plane(pl, w0[dx]);
                     }
                 }
             }
+        };
+        Batch A, B;
+        bool moreA = issue(A, mass_tag);
+        while (moreA) {
+            const bool moreB = issue(B, mass_tag);   // in flight during A
+            consume(A);
+            if (!moreB) break;
+            moreA = issue(A, mass_tag);              // in flight during B
+            consume(B);
         }
+    };
+    if (((n0 & (n0 - 1)) | (n1 & (n1 - 1)) | (n2 & (n2 - 1))) == 0
+        && (n0 | n1 | n2) <= ((int64_t)1 << 31)) {
+        if (mass) particle_loop(std::true_type{}, std::true_type{});
+        else particle_loop(std::true_type{}, std::false_type{});
+    } else {
+        if (mass) particle_loop(std::false_type{}, std::true_type{});
+        else particle_loop(std::false_type{}, std::false_type{});
     }
     __syncthreads();
 
