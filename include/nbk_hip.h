@@ -88,10 +88,11 @@ int nbk_paint_f64(const double* pos, const double* mass, int64_t n,
                   double* mesh, int64_t x0, int64_t nx_local,
                   void* stream);
 
-/* paint for cell-sorted input: TSC/PCS deposits accumulate in an LDS
- * window per contiguous particle run and flush once (CIC falls through
- * to nbk_paint_f64).  Same semantics as nbk_paint_f64; the caller must
- * know the input is cell-ordered (the bucket sort's output is). */
+/* paint for cell-sorted input: PCS deposits accumulate in an LDS window
+ * per contiguous particle run and flush once (CIC and TSC go to
+ * nbk_paint_f64, which is faster for them).  Same semantics as
+ * nbk_paint_f64; the caller must know the input is cell-ordered (the
+ * bucket sort's output is). */
 int nbk_paint_sorted_f64(const double* pos, const double* mass, int64_t n,
                          const int64_t nmesh[3], const double box[3],
                          int window, double shift,

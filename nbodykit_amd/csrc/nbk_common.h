@@ -126,7 +126,8 @@ __device__ __forceinline__ void nbk_sync_lds() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// bit-reversal for the in-tile FFT (shared with nbk_fft.hip's local copy)
+// bit-reversal of the low `bits` bits (nbk_fft.hip's line FFTs and the
+// gather paint's in-tile FFT)
 __device__ __forceinline__ int nbk_bitrev(int j, int bits) {
     return (int)(__brev((unsigned)j) >> (32 - bits));
 }

@@ -60,10 +60,6 @@ double* get_twiddles(int64_t N) {
     return dev;
 }
 
-__device__ __forceinline__ int bitrev(int j, int bits) {
-    return (int)(__brev((unsigned)j) >> (32 - bits));
-}
-
 // Radix-4 variant: pairs of radix-2 DIT stages fused into one 4-point
 // butterfly over the SAME bit-reversed input order, halving the
 // __syncthreads count and LDS round trips (the strided passes are
@@ -155,7 +151,7 @@ __global__ void kfft_r2c_z(const double* __restrict__ real,
 
     const cdouble* g = (const cdouble*)(real + line * nz);  // packed pairs
     for (int q = threadIdx.x; q < m; q += blockDim.x)
-        buf[bitrev(q, bits)] = g[q];
+        buf[nbk_bitrev(q, bits)] = g[q];
     __syncthreads();
 
     lds_fft4<false>(buf, m, 1, 1, table, m);
@@ -208,7 +204,7 @@ __global__ void kfft_c2r_z(const double* __restrict__ cplx,
         const cdouble WO = cscale(csub(Xk, Xm), 0.5);
         const cdouble O = cmul(cconj(table[k]), WO);
         const cdouble Z = {E.re - O.im, E.im + O.re};    // E + i O
-        buf[bitrev(k, bits)] = Z;
+        buf[nbk_bitrev(k, bits)] = Z;
     }
     __syncthreads();
 
@@ -261,7 +257,7 @@ __global__ void kfft_c_strided(double* __restrict__ data,
         for (int q = 0; q < 8; q++) {
             const int w = base + q * (int)blockDim.x + (int)threadIdx.x;
             if (w < total)
-                buf[bitrev(w / TI, bits) * TI + (w % TI)] = r[q];
+                buf[nbk_bitrev(w / TI, bits) * TI + (w % TI)] = r[q];
         }
     }
     __syncthreads();
@@ -517,7 +513,7 @@ __global__ void kxfft_bin(const double* __restrict__ data,
     for (int q = 0; q < NLD; q++) {                                        \
         const int w_ = q * T + t;                                          \
         if (w_ < n0 * TI) {                                                \
-            const int at_ = bitrev(w_ / TI, bits) * W + (w_ % TI);         \
+            const int at_ = nbk_bitrev(w_ / TI, bits) * W + (w_ % TI);     \
             buf[at_] = r[q];                                               \
             if (IL)                                                        \
                 buf2[at_] = r2[q];                                         \

@@ -57,8 +57,29 @@ __device__ __forceinline__ void merged_deposit(double* __restrict__ mesh,
         atomicAdd(&mesh[addr], val);
 }
 
-// per-axis window weights + unwrapped base cell (shared by the tiled
-// kernel's two paths; the main kpaint keeps its inlined version)
+// readout-only id of the nearest-grid-point "window" (no weights, not a
+// paint window; follows NBK_WINDOW_PCS)
+constexpr int WINDOW_NNB = 3;
+
+// cells per axis a window's stencil covers
+template <int WINDOW>
+constexpr int window_support() {
+    return (WINDOW == NBK_WINDOW_CIC) ? 2
+         : (WINDOW == NBK_WINDOW_TSC) ? 3 : 4;
+}
+
+// unwrapped base cell (first cell of the stencil) of mesh coordinate u:
+// TSC is centred on the nearest grid point, CIC and PCS on the cell
+template <int WINDOW>
+__device__ __forceinline__ int64_t base_cell(double u) {
+    const double f = floor(WINDOW == NBK_WINDOW_TSC ? u + 0.5 : u);
+    return (int64_t)f - (WINDOW == NBK_WINDOW_CIC ? 0 : 1);
+}
+
+// per-axis window weights + unwrapped base cell: the one definition of
+// the three window shapes, shared by every paint kernel and the readout
+// (their adjointness rests on it).  The three axes are interleaved on
+// purpose — the gather kernel's instruction schedule was tuned on it.
 template <int WINDOW, int SUP>
 __device__ __forceinline__ void paint_weights(double u0, double u1,
                                               double u2,
@@ -69,14 +90,16 @@ __device__ __forceinline__ void paint_weights(double u0, double u1,
                                               int64_t& b2) {
     if (WINDOW == NBK_WINDOW_CIC) {
         const double f0 = floor(u0), f1 = floor(u1), f2 = floor(u2);
-        b0 = (int64_t)f0; b1 = (int64_t)f1; b2 = (int64_t)f2;
+        b0 = base_cell<WINDOW>(u0); b1 = base_cell<WINDOW>(u1);
+        b2 = base_cell<WINDOW>(u2);
         w0[SUP - 1] = u0 - f0; w0[0] = 1.0 - (u0 - f0);
         w1[SUP - 1] = u1 - f1; w1[0] = 1.0 - (u1 - f1);
         w2[SUP - 1] = u2 - f2; w2[0] = 1.0 - (u2 - f2);
     } else if (WINDOW == NBK_WINDOW_TSC) {
         const double f0 = floor(u0 + 0.5), f1 = floor(u1 + 0.5),
                      f2 = floor(u2 + 0.5);
-        b0 = (int64_t)f0 - 1; b1 = (int64_t)f1 - 1; b2 = (int64_t)f2 - 1;
+        b0 = base_cell<WINDOW>(u0); b1 = base_cell<WINDOW>(u1);
+        b2 = base_cell<WINDOW>(u2);
         #pragma unroll
         for (int d = 0; d < 3; d++) {
             const double s0 = u0 - (f0 + d - 1);
@@ -92,7 +115,8 @@ __device__ __forceinline__ void paint_weights(double u0, double u1,
         }
     } else {   // PCS
         const double f0 = floor(u0), f1 = floor(u1), f2 = floor(u2);
-        b0 = (int64_t)f0 - 1; b1 = (int64_t)f1 - 1; b2 = (int64_t)f2 - 1;
+        b0 = base_cell<WINDOW>(u0); b1 = base_cell<WINDOW>(u1);
+        b2 = base_cell<WINDOW>(u2);
         #pragma unroll
         for (int d = 0; d < 4; d++) {
             const double s0 = fabs(u0 - (f0 + d - 1));
@@ -122,8 +146,7 @@ __global__ void kpaint(const double* __restrict__ px,
                        double* __restrict__ mesh,
                        int64_t x0, int64_t nx_local)
 {
-    constexpr int SUP = (WINDOW == NBK_WINDOW_CIC) ? 2
-                      : (WINDOW == NBK_WINDOW_TSC) ? 3 : 4;
+    constexpr int SUP = window_support<WINDOW>();
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     // iterate whole waves so the shuffle stays collective at the tail
@@ -140,50 +163,7 @@ __global__ void kpaint(const double* __restrict__ px,
 
         double w0[SUP], w1[SUP], w2[SUP];
         int64_t b0, b1, b2;   // base cell per axis
-
-        if (WINDOW == NBK_WINDOW_CIC) {
-            const double f0 = floor(u0), f1 = floor(u1), f2 = floor(u2);
-            b0 = (int64_t)f0; b1 = (int64_t)f1; b2 = (int64_t)f2;
-            w0[1] = u0 - f0; w0[0] = 1.0 - w0[1];
-            w1[1] = u1 - f1; w1[0] = 1.0 - w1[1];
-            w2[1] = u2 - f2; w2[0] = 1.0 - w2[1];
-        } else if (WINDOW == NBK_WINDOW_TSC) {
-            // centered on the nearest grid point; support 3
-            const double f0 = floor(u0 + 0.5), f1 = floor(u1 + 0.5),
-                         f2 = floor(u2 + 0.5);
-            b0 = (int64_t)f0 - 1; b1 = (int64_t)f1 - 1; b2 = (int64_t)f2 - 1;
-            #pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const double s0 = u0 - (f0 + d - 1);
-                const double s1 = u1 - (f1 + d - 1);
-                const double s2 = u2 - (f2 + d - 1);
-                const double a0 = fabs(s0), a1 = fabs(s1), a2 = fabs(s2);
-                w0[d] = a0 < 0.5 ? 0.75 - s0 * s0
-                                 : 0.5 * (1.5 - a0) * (1.5 - a0);
-                w1[d] = a1 < 0.5 ? 0.75 - s1 * s1
-                                 : 0.5 * (1.5 - a1) * (1.5 - a1);
-                w2[d] = a2 < 0.5 ? 0.75 - s2 * s2
-                                 : 0.5 * (1.5 - a2) * (1.5 - a2);
-            }
-        } else {  // PCS, support 4 (cubic B-spline)
-            const double f0 = floor(u0), f1 = floor(u1), f2 = floor(u2);
-            b0 = (int64_t)f0 - 1; b1 = (int64_t)f1 - 1; b2 = (int64_t)f2 - 1;
-            #pragma unroll
-            for (int d = 0; d < 4; d++) {
-                const double s0 = fabs(u0 - (f0 + d - 1));
-                const double s1 = fabs(u1 - (f1 + d - 1));
-                const double s2 = fabs(u2 - (f2 + d - 1));
-                w0[d] = s0 < 1.0
-                    ? (4.0 - 6.0 * s0 * s0 + 3.0 * s0 * s0 * s0) / 6.0
-                    : (2.0 - s0) * (2.0 - s0) * (2.0 - s0) / 6.0;
-                w1[d] = s1 < 1.0
-                    ? (4.0 - 6.0 * s1 * s1 + 3.0 * s1 * s1 * s1) / 6.0
-                    : (2.0 - s1) * (2.0 - s1) * (2.0 - s1) / 6.0;
-                w2[d] = s2 < 1.0
-                    ? (4.0 - 6.0 * s2 * s2 + 3.0 * s2 * s2 * s2) / 6.0
-                    : (2.0 - s2) * (2.0 - s2) * (2.0 - s2) / 6.0;
-            }
-        }
+        paint_weights<WINDOW, SUP>(u0, u1, u2, w0, w1, w2, b0, b1, b2);
 
         #pragma unroll
         for (int dx = 0; dx < SUP; dx++) {
@@ -209,14 +189,15 @@ __global__ void kpaint(const double* __restrict__ px,
     }
 }
 
-// LDS-windowed paint for CELL-SORTED input (TSC/PCS) — each block owns
-// a contiguous particle run, accumulates all support^3 deposits into an
-// LDS window covering the run's (x, y) line span x the full z axis
-// (native ds_add_f64), then flushes the window once with a sequential
-// stream of global atomics.  Cuts global atomics from 27 (TSC) / 64
-// (PCS) per particle to ~window/run and makes them address-sequential —
-// the direct kernel is atomic-issue-bound there (41 vs 127 Gatomic/s
-// for CIC's lane-sequential pattern).  Blocks whose particles span a
+// LDS-windowed paint for CELL-SORTED input (instantiated for PCS only,
+// see nbk_paint_sorted_f64) — each block owns a contiguous particle
+// run, accumulates all support^3 deposits into an LDS window covering
+// the run's (x, y) line span x the full z axis (native ds_add_f64),
+// then flushes the window once with a sequential stream of global
+// atomics.  Cuts global atomics from 64 per PCS particle to ~window/run
+// and makes them address-sequential — the direct kernel is
+// atomic-issue-bound there (41 vs 127 Gatomic/s for CIC's
+// lane-sequential pattern).  Blocks whose particles span a
 // window larger than the LDS budget (scrambled input must never reach
 // this kernel) fall back to direct per-particle atomics.
 #define NBK_TILE_PPB 1024          /* particles per block */
@@ -233,7 +214,7 @@ __global__ void kpaint_tiled(const double* __restrict__ px,
                              double* __restrict__ mesh,
                              int64_t x0, int64_t nx_local)
 {
-    constexpr int SUP = (WINDOW == NBK_WINDOW_TSC) ? 3 : 4;
+    constexpr int SUP = window_support<WINDOW>();
     __shared__ double buf[NBK_TILE_MAX_CELLS];
     __shared__ int s_min0, s_max0, s_min1, s_max1;
 
@@ -251,14 +232,8 @@ __global__ void kpaint_tiled(const double* __restrict__ px,
     for (int64_t i = ibeg + threadIdx.x; i < iend; i += blockDim.x) {
         const double u0 = px[i] * invH0 + shift;
         const double u1 = py[i] * invH1 + shift;
-        int b0, b1;
-        if (WINDOW == NBK_WINDOW_TSC) {
-            b0 = (int)floor(u0 + 0.5) - 1;
-            b1 = (int)floor(u1 + 0.5) - 1;
-        } else {
-            b0 = (int)floor(u0) - 1;
-            b1 = (int)floor(u1) - 1;
-        }
+        const int b0 = (int)base_cell<WINDOW>(u0);
+        const int b1 = (int)base_cell<WINDOW>(u1);
         mn0 = min(mn0, b0); mx0 = max(mx0, b0);
         mn1 = min(mn1, b1); mx1 = max(mx1, b1);
     }
@@ -388,9 +363,8 @@ __global__ void kpaint_gather(const double* __restrict__ px,
                                   (NBK_PAINT_PHASES): bit1 deposits,
                                   bit2 FFT+flush; 3 = real kernel */)
 {
-    constexpr int SUP = (WINDOW == NBK_WINDOW_CIC) ? 2
-                      : (WINDOW == NBK_WINDOW_TSC) ? 3 : 4;
-    if (PT > 0) P = PT;                   // compile-time plane count
+    constexpr int SUP = window_support<WINDOW>();
+    if (PT > 0) P = PT;                  // compile-time plane count
     extern __shared__ double tile[];      // P * RG * (n2 [+4]) doubles
     const int64_t sp = DOFFT ? n2 + 4 : n2;   // padded row stride
     const int64_t tiles_per_plane = n1 / RG;
@@ -716,9 +690,8 @@ __global__ void kpaint_gather(const double* __restrict__ px,
         // element-exact against numpy).  Odd log2(m): one multiply-free
         // radix-2 stage first.
         {
-            const int fbits = 31 - __clz((unsigned)m);
             int len = 2;
-            if (fbits & 1) {
+            if (bits & 1) {
                 for (int q = lane; q < (m >> 1); q += 64) {
                     const int i0 = 2 * q;
                     const cdouble u = z[i0];
@@ -797,7 +770,7 @@ __global__ void kreadout(const double* __restrict__ px,
         const double u0 = px[i] * invH0, u1 = py[i] * invH1,
                      u2 = pz[i] * invH2;
 
-        if (WINDOW == 3) {    // nnb
+        if (WINDOW == WINDOW_NNB) {
             const int64_t gx = wrap_idx((int64_t)floor(u0 + 0.5), n0);
             const int64_t gy = wrap_idx((int64_t)floor(u1 + 0.5), n1);
             const int64_t gz = wrap_idx((int64_t)floor(u2 + 0.5), n2);
@@ -806,54 +779,10 @@ __global__ void kreadout(const double* __restrict__ px,
             continue;
         }
 
-        constexpr int SUP = (WINDOW == NBK_WINDOW_CIC) ? 2
-                          : (WINDOW == NBK_WINDOW_TSC) ? 3 : 4;
+        constexpr int SUP = window_support<WINDOW>();
         double w0[SUP], w1[SUP], w2[SUP];
         int64_t b0, b1, b2;
-        if (WINDOW == NBK_WINDOW_CIC) {
-            const double f0 = floor(u0), f1 = floor(u1), f2 = floor(u2);
-            b0 = (int64_t)f0; b1 = (int64_t)f1; b2 = (int64_t)f2;
-            w0[1] = u0 - f0; w0[0] = 1.0 - w0[1];
-            w1[1] = u1 - f1; w1[0] = 1.0 - w1[1];
-            w2[1] = u2 - f2; w2[0] = 1.0 - w2[1];
-        } else if (WINDOW == NBK_WINDOW_TSC) {
-            const double f0 = floor(u0 + 0.5), f1 = floor(u1 + 0.5),
-                         f2 = floor(u2 + 0.5);
-            b0 = (int64_t)f0 - 1; b1 = (int64_t)f1 - 1;
-            b2 = (int64_t)f2 - 1;
-            #pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const double s0 = u0 - (f0 + d - 1);
-                const double s1 = u1 - (f1 + d - 1);
-                const double s2 = u2 - (f2 + d - 1);
-                const double a0 = fabs(s0), a1 = fabs(s1), a2 = fabs(s2);
-                w0[d] = a0 < 0.5 ? 0.75 - s0 * s0
-                                 : 0.5 * (1.5 - a0) * (1.5 - a0);
-                w1[d] = a1 < 0.5 ? 0.75 - s1 * s1
-                                 : 0.5 * (1.5 - a1) * (1.5 - a1);
-                w2[d] = a2 < 0.5 ? 0.75 - s2 * s2
-                                 : 0.5 * (1.5 - a2) * (1.5 - a2);
-            }
-        } else {
-            const double f0 = floor(u0), f1 = floor(u1), f2 = floor(u2);
-            b0 = (int64_t)f0 - 1; b1 = (int64_t)f1 - 1;
-            b2 = (int64_t)f2 - 1;
-            #pragma unroll
-            for (int d = 0; d < 4; d++) {
-                const double s0 = fabs(u0 - (f0 + d - 1));
-                const double s1 = fabs(u1 - (f1 + d - 1));
-                const double s2 = fabs(u2 - (f2 + d - 1));
-                w0[d] = s0 < 1.0
-                    ? (4.0 - 6.0 * s0 * s0 + 3.0 * s0 * s0 * s0) / 6.0
-                    : (2.0 - s0) * (2.0 - s0) * (2.0 - s0) / 6.0;
-                w1[d] = s1 < 1.0
-                    ? (4.0 - 6.0 * s1 * s1 + 3.0 * s1 * s1 * s1) / 6.0
-                    : (2.0 - s1) * (2.0 - s1) * (2.0 - s1) / 6.0;
-                w2[d] = s2 < 1.0
-                    ? (4.0 - 6.0 * s2 * s2 + 3.0 * s2 * s2 * s2) / 6.0
-                    : (2.0 - s2) * (2.0 - s2) * (2.0 - s2) / 6.0;
-            }
-        }
+        paint_weights<WINDOW, SUP>(u0, u1, u2, w0, w1, w2, b0, b1, b2);
 
         double acc = 0.0;
         #pragma unroll
@@ -885,6 +814,22 @@ int grid_for(int64_t n, int block) {
     return (int)g;
 }
 
+// The one place a runtime window id becomes a template argument:
+// calls f(std::integral_constant<int, W>{}) for the three paint
+// windows; false = unknown id, f not called.
+template <class F>
+bool with_window(int window, F&& f) {
+    switch (window) {
+    case NBK_WINDOW_CIC:
+        f(std::integral_constant<int, NBK_WINDOW_CIC>{}); return true;
+    case NBK_WINDOW_TSC:
+        f(std::integral_constant<int, NBK_WINDOW_TSC>{}); return true;
+    case NBK_WINDOW_PCS:
+        f(std::integral_constant<int, NBK_WINDOW_PCS>{}); return true;
+    }
+    return false;
+}
+
 }  // namespace
 
 extern "C" int nbk_paint_f64(const double* pos, const double* mass, int64_t n,
@@ -906,23 +851,13 @@ extern "C" int nbk_paint_f64(const double* pos, const double* mass, int64_t n,
     hipStream_t s = (hipStream_t)stream;
     const double *px = pos, *py = pos + n, *pz = pos + 2 * n;
 
-    switch (window) {
-    case NBK_WINDOW_CIC:
-        hipLaunchKernelGGL(kpaint<NBK_WINDOW_CIC>, dim3(grid), dim3(block), 0, s,
-                           px, py, pz, mass, n, nmesh[0], nmesh[1], nmesh[2],
-                           invH0, invH1, invH2, shift, mesh, x0, nx_local);
-        break;
-    case NBK_WINDOW_TSC:
-        hipLaunchKernelGGL(kpaint<NBK_WINDOW_TSC>, dim3(grid), dim3(block), 0, s,
-                           px, py, pz, mass, n, nmesh[0], nmesh[1], nmesh[2],
-                           invH0, invH1, invH2, shift, mesh, x0, nx_local);
-        break;
-    case NBK_WINDOW_PCS:
-        hipLaunchKernelGGL(kpaint<NBK_WINDOW_PCS>, dim3(grid), dim3(block), 0, s,
-                           px, py, pz, mass, n, nmesh[0], nmesh[1], nmesh[2],
-                           invH0, invH1, invH2, shift, mesh, x0, nx_local);
-        break;
-    default:
+    if (!with_window(window, [&](auto w) {
+            hipLaunchKernelGGL(kpaint<decltype(w)::value>, dim3(grid),
+                               dim3(block), 0, s, px, py, pz, mass, n,
+                               nmesh[0], nmesh[1], nmesh[2],
+                               invH0, invH1, invH2, shift, mesh, x0,
+                               nx_local);
+        })) {
         NBK_SET_ERR("nbk_paint_f64: unknown window id %d", window);
         return NBK_ERR_ARG;
     }
@@ -941,14 +876,11 @@ extern "C" int nbk_paint_sorted_f64(const double* pos, const double* mass,
     // shows all TSC variants 71-88% instruction-ISSUE-stalled, so
     // rerouting deposits through LDS buys nothing there.  Only PCS
     // (64 deposits, flush ~3x cheaper than direct) takes the tiled
-    // path; CIC and TSC keep the direct kernel.
-    if (window == NBK_WINDOW_CIC || window == NBK_WINDOW_TSC || n == 0)
+    // path; CIC and TSC keep the direct kernel, which also rejects an
+    // unknown id.
+    if (window != NBK_WINDOW_PCS || n == 0)
         return nbk_paint_f64(pos, mass, n, nmesh, box, window, shift,
                              mesh, x0, nx_local, stream);
-    if (window != NBK_WINDOW_TSC && window != NBK_WINDOW_PCS) {
-        NBK_SET_ERR("nbk_paint_sorted_f64: unknown window id %d", window);
-        return NBK_ERR_ARG;
-    }
     const double invH0 = nmesh[0] / box[0];
     const double invH1 = nmesh[1] / box[1];
     const double invH2 = nmesh[2] / box[2];
@@ -959,18 +891,11 @@ extern "C" int nbk_paint_sorted_f64(const double* pos, const double* mass,
     }
     hipStream_t s = (hipStream_t)stream;
     const double *px = pos, *py = pos + n, *pz = pos + 2 * n;
-    if (window == NBK_WINDOW_TSC)
-        hipLaunchKernelGGL(kpaint_tiled<NBK_WINDOW_TSC>,
-                           dim3((uint32_t)grid), dim3(256), 0, s,
-                           px, py, pz, mass, n, nmesh[0], nmesh[1],
-                           nmesh[2], invH0, invH1, invH2, shift, mesh,
-                           x0, nx_local);
-    else
-        hipLaunchKernelGGL(kpaint_tiled<NBK_WINDOW_PCS>,
-                           dim3((uint32_t)grid), dim3(256), 0, s,
-                           px, py, pz, mass, n, nmesh[0], nmesh[1],
-                           nmesh[2], invH0, invH1, invH2, shift, mesh,
-                           x0, nx_local);
+    hipLaunchKernelGGL(kpaint_tiled<NBK_WINDOW_PCS>,
+                       dim3((uint32_t)grid), dim3(256), 0, s,
+                       px, py, pz, mass, n, nmesh[0], nmesh[1],
+                       nmesh[2], invH0, invH1, invH2, shift, mesh,
+                       x0, nx_local);
     NBK_CHECK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -989,32 +914,15 @@ extern "C" int nbk_readout_f64(const double* pos, int64_t n,
     const double iH0 = nmesh[0] / box[0];
     const double iH1 = nmesh[1] / box[1];
     const double iH2 = nmesh[2] / box[2];
-    switch (window) {
-    case NBK_WINDOW_CIC:
-        hipLaunchKernelGGL(kreadout<NBK_WINDOW_CIC>, dim3(grid), dim3(block),
-                           0, s, pos, pos + n, pos + 2 * n, n,
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(kreadout<decltype(w)::value>, dim3(grid),
+                           dim3(block), 0, s, pos, pos + n, pos + 2 * n, n,
                            nmesh[0], nmesh[1], nmesh[2], iH0, iH1, iH2,
                            mesh, x0, nx_local, out);
-        break;
-    case NBK_WINDOW_TSC:
-        hipLaunchKernelGGL(kreadout<NBK_WINDOW_TSC>, dim3(grid), dim3(block),
-                           0, s, pos, pos + n, pos + 2 * n, n,
-                           nmesh[0], nmesh[1], nmesh[2], iH0, iH1, iH2,
-                           mesh, x0, nx_local, out);
-        break;
-    case NBK_WINDOW_PCS:
-        hipLaunchKernelGGL(kreadout<NBK_WINDOW_PCS>, dim3(grid), dim3(block),
-                           0, s, pos, pos + n, pos + 2 * n, n,
-                           nmesh[0], nmesh[1], nmesh[2], iH0, iH1, iH2,
-                           mesh, x0, nx_local, out);
-        break;
-    case 3:   /* nnb */
-        hipLaunchKernelGGL(kreadout<3>, dim3(grid), dim3(block), 0, s,
-                           pos, pos + n, pos + 2 * n, n,
-                           nmesh[0], nmesh[1], nmesh[2], iH0, iH1, iH2,
-                           mesh, x0, nx_local, out);
-        break;
-    default:
+    };
+    if (window == WINDOW_NNB) {
+        launch(std::integral_constant<int, WINDOW_NNB>{});
+    } else if (!with_window(window, launch)) {
         NBK_SET_ERR("nbk_readout_f64: unknown window id %d", window);
         return NBK_ERR_ARG;
     }
@@ -1077,21 +985,22 @@ static void nbk_pick_tile(int64_t nx_local, int64_t n1, int64_t n2,
     *RG_out = bRG;
 }
 
-extern "C" int nbk_paint_gather_f64(const double* pos, const double* mass,
-                                    int64_t n, const int64_t nmesh[3],
-                                    const double box[3],
-                                    int window, double shift,
-                                    const int* rowtab,
-                                    double* mesh, int64_t x0,
-                                    int64_t nx_local, int accumulate,
-                                    int pair_gs, void* stream)
+// The launch behind nbk_paint_gather_f64 (DOFFT = false: `out` is the
+// real slab, written or accumulated into) and nbk_paint_gather_fft_f64
+// (DOFFT = true: `out` is the z half-spectrum, rows padded by 4 doubles
+// in LDS, `table`/`scale` feed the fused FFT).  `who` names the entry
+// point in the error texts; the callers have validated n2.
+template <bool DOFFT>
+static int paint_gather_launch(const char* who, const double* pos,
+                               const double* mass, int64_t n,
+                               const int64_t nmesh[3], const double box[3],
+                               int window, double shift, const int* rowtab,
+                               double* out, int64_t x0, int64_t nx_local,
+                               int accumulate, const cdouble* table,
+                               double scale, int pair_gs, void* stream)
 {
     const int64_t n0 = nmesh[0], n1 = nmesh[1], n2 = nmesh[2];
-    if (n2 > 20480) {
-        NBK_SET_ERR("nbk_paint_gather_f64: no LDS tile for n1=%lld "
-                    "n2=%lld", (long long)n1, (long long)n2);
-        return NBK_ERR_UNSUPPORTED;
-    }
+    const int64_t pad = DOFFT ? 4 : 0;    // the kernel's row stride - n2
     // delta = b0 - ixc range per window/shift: source
     // planes/rows = [xlo, xhi] around the owner
     const bool sh = shift != 0.0;
@@ -1103,7 +1012,7 @@ extern "C" int nbk_paint_gather_f64(const double* pos, const double* mass,
     } else if (window == NBK_WINDOW_PCS) {
         sup = 4; dmin = -1; dmax = sh ? 0 : -1;
     } else {
-        NBK_SET_ERR("nbk_paint_gather_f64: bad window %d", window);
+        NBK_SET_ERR("%s: bad window %d", who, window);
         return NBK_ERR_ARG;
     }
     const int xlo = -sup + 1 - dmax;
@@ -1116,54 +1025,58 @@ extern "C" int nbk_paint_gather_f64(const double* pos, const double* mass,
         // group size (one plane x one y-group)
         P = 1;
         RG = 1 << pair_gs;
-        if ((int64_t)RG * n2 * 8 > 160 * 1024 || n1 % RG) {
-            NBK_SET_ERR("nbk_paint_gather_f64: bad pair_gs=%d", pair_gs);
+        if ((int64_t)RG * (n2 + pad) * 8 > 160 * 1024 || n1 % RG) {
+            NBK_SET_ERR("%s: bad pair_gs=%d", who, pair_gs);
             return NBK_ERR_ARG;
         }
     } else {
-        nbk_pick_tile(nx_local, n1, n2, 0, span, span, &P, &RG);
+        nbk_pick_tile(nx_local, n1, n2, pad, span, span, &P, &RG);
     }
     const int64_t grid = (nx_local / P) * (n1 / RG);
-    const size_t lds = (size_t)P * RG * n2 * sizeof(double);
+    const size_t lds = (size_t)P * RG * (n2 + pad) * sizeof(double);
     hipStream_t s = (hipStream_t)stream;
-    if (lds > 64 * 1024) {
-        const void* fns[6] = {
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_CIC, false, 0>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_TSC, false, 0>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_PCS, false, 0>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_CIC, false, 1>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_TSC, false, 1>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_PCS, false, 1>)};
-        (void)hipFuncSetAttribute(fns[window + (P == 1 ? 3 : 0)],
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    #define NBK_LAUNCH_GATHER(W, PT) \
-        hipLaunchKernelGGL((kpaint_gather<W, false, PT>), \
-                           dim3((uint32_t)grid), \
-                           dim3(1024), lds, s, pos, pos + n, pos + 2 * n, \
-                           mass, n, n0, n1, n2, \
-                           n0 / box[0], n1 / box[1], n2 / box[2], shift, \
-                           rowtab, mesh, x0, nx_local, RG, P, xlo, xhi, \
-                           accumulate, (const cdouble*)nullptr, 1.0, \
-                           pair_gs, nbk_paint_phases())
-    if (P == 1) {
-        if (window == NBK_WINDOW_CIC) NBK_LAUNCH_GATHER(NBK_WINDOW_CIC, 1);
-        else if (window == NBK_WINDOW_TSC) NBK_LAUNCH_GATHER(NBK_WINDOW_TSC, 1);
-        else NBK_LAUNCH_GATHER(NBK_WINDOW_PCS, 1);
-    } else {
-        if (window == NBK_WINDOW_CIC) NBK_LAUNCH_GATHER(NBK_WINDOW_CIC, 0);
-        else if (window == NBK_WINDOW_TSC) NBK_LAUNCH_GATHER(NBK_WINDOW_TSC, 0);
-        else NBK_LAUNCH_GATHER(NBK_WINDOW_PCS, 0);
-    }
-    #undef NBK_LAUNCH_GATHER
+    // PT: the kernel's compile-time plane count (1, or 0 = runtime P)
+    auto launch = [&](auto w, auto pt) {
+        auto* kernel = &kpaint_gather<decltype(w)::value, DOFFT,
+                                      decltype(pt)::value>;
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute(
+                reinterpret_cast<const void*>(kernel),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(1024), lds,
+                           s, pos, pos + n, pos + 2 * n, mass, n,
+                           n0, n1, n2,
+                           n0 / box[0], n1 / box[1], n2 / box[2], shift,
+                           rowtab, out, x0, nx_local, RG, P, xlo, xhi,
+                           accumulate, table, scale, pair_gs,
+                           nbk_paint_phases());
+    };
+    with_window(window, [&](auto w) {
+        if (P == 1) launch(w, std::integral_constant<int, 1>{});
+        else launch(w, std::integral_constant<int, 0>{});
+    });
     NBK_CHECK_HIP(hipGetLastError());
     return NBK_OK;
+}
+
+extern "C" int nbk_paint_gather_f64(const double* pos, const double* mass,
+                                    int64_t n, const int64_t nmesh[3],
+                                    const double box[3],
+                                    int window, double shift,
+                                    const int* rowtab,
+                                    double* mesh, int64_t x0,
+                                    int64_t nx_local, int accumulate,
+                                    int pair_gs, void* stream)
+{
+    if (nmesh[2] > 20480) {
+        NBK_SET_ERR("nbk_paint_gather_f64: no LDS tile for n1=%lld "
+                    "n2=%lld", (long long)nmesh[1], (long long)nmesh[2]);
+        return NBK_ERR_UNSUPPORTED;
+    }
+    return paint_gather_launch<false>(
+        "nbk_paint_gather_f64", pos, mass, n, nmesh, box, window, shift,
+        rowtab, mesh, x0, nx_local, accumulate, nullptr, 1.0, pair_gs,
+        stream);
 }
 
 extern "C" int nbk_paint_gather_fft_f64(const double* pos,
@@ -1176,7 +1089,7 @@ extern "C" int nbk_paint_gather_fft_f64(const double* pos,
                                         int64_t nx_local, double scale,
                                         int pair_gs, void* stream)
 {
-    const int64_t n0 = nmesh[0], n1 = nmesh[1], n2 = nmesh[2];
+    const int64_t n1 = nmesh[1], n2 = nmesh[2];
     if (n2 < 8 || n2 > 4096 || (n2 & (n2 - 1))) {
         NBK_SET_ERR("nbk_paint_gather_fft_f64: n2=%lld not a supported "
                     "FFT length", (long long)n2);
@@ -1192,73 +1105,8 @@ extern "C" int nbk_paint_gather_fft_f64(const double* pos,
         NBK_SET_ERR("twiddle alloc failed");
         return NBK_ERR_HIP;
     }
-    const bool sh = shift != 0.0;
-    int sup, dmin, dmax;
-    if (window == NBK_WINDOW_CIC) {
-        sup = 2; dmin = 0; dmax = sh ? 1 : 0;
-    } else if (window == NBK_WINDOW_TSC) {
-        sup = 3; dmin = sh ? 0 : -1; dmax = 0;
-    } else if (window == NBK_WINDOW_PCS) {
-        sup = 4; dmin = -1; dmax = sh ? 0 : -1;
-    } else {
-        NBK_SET_ERR("nbk_paint_gather_fft_f64: bad window %d", window);
-        return NBK_ERR_ARG;
-    }
-    const int xlo = -sup + 1 - dmax;
-    const int xhi = -dmin;
-    const int span = xhi - xlo;
-
-    int P, RG;
-    if (pair_gs >= 0) {
-        P = 1;
-        RG = 1 << pair_gs;
-        if ((int64_t)RG * (n2 + 4) * 8 > 160 * 1024 || n1 % RG) {
-            NBK_SET_ERR("nbk_paint_gather_fft_f64: bad pair_gs=%d",
-                        pair_gs);
-            return NBK_ERR_ARG;
-        }
-    } else {
-        nbk_pick_tile(nx_local, n1, n2, 4, span, span, &P, &RG);
-    }
-    const int64_t grid = (nx_local / P) * (n1 / RG);
-    const size_t lds = (size_t)P * RG * (n2 + 4) * sizeof(double);
-    hipStream_t s = (hipStream_t)stream;
-    if (lds > 64 * 1024) {
-        const void* fns[6] = {
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_CIC, true, 0>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_TSC, true, 0>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_PCS, true, 0>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_CIC, true, 1>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_TSC, true, 1>),
-            reinterpret_cast<const void*>(
-                &kpaint_gather<NBK_WINDOW_PCS, true, 1>)};
-        (void)hipFuncSetAttribute(fns[window + (P == 1 ? 3 : 0)],
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    #define NBK_LAUNCH_GFFT(W, PT) \
-        hipLaunchKernelGGL((kpaint_gather<W, true, PT>), \
-                           dim3((uint32_t)grid), \
-                           dim3(1024), lds, s, pos, pos + n, pos + 2 * n, \
-                           mass, n, n0, n1, n2, \
-                           n0 / box[0], n1 / box[1], n2 / box[2], shift, \
-                           rowtab, zspec, x0, nx_local, RG, P, xlo, \
-                           xhi, 0, (const cdouble*)table, scale, \
-                           pair_gs, nbk_paint_phases())
-    if (P == 1) {
-        if (window == NBK_WINDOW_CIC) NBK_LAUNCH_GFFT(NBK_WINDOW_CIC, 1);
-        else if (window == NBK_WINDOW_TSC) NBK_LAUNCH_GFFT(NBK_WINDOW_TSC, 1);
-        else NBK_LAUNCH_GFFT(NBK_WINDOW_PCS, 1);
-    } else {
-        if (window == NBK_WINDOW_CIC) NBK_LAUNCH_GFFT(NBK_WINDOW_CIC, 0);
-        else if (window == NBK_WINDOW_TSC) NBK_LAUNCH_GFFT(NBK_WINDOW_TSC, 0);
-        else NBK_LAUNCH_GFFT(NBK_WINDOW_PCS, 0);
-    }
-    #undef NBK_LAUNCH_GFFT
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    return paint_gather_launch<true>(
+        "nbk_paint_gather_fft_f64", pos, mass, n, nmesh, box, window,
+        shift, rowtab, zspec, x0, nx_local, 0, (const cdouble*)table,
+        scale, pair_gs, stream);
 }

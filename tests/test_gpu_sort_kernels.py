@@ -1,8 +1,8 @@
 """
-Kernel-level tests of the paint locality sorts and the ownership-gather
-paint, called through the C ABI and compared with plain numpy
-(sort_reference.py) and with oracle.paint — never with another GPU
-kernel.
+Kernel-level tests of the paint locality sorts, the ownership-gather
+paint, the scatter paints and the readout, called through the C ABI and
+compared with plain numpy (sort_reference.py) and with oracle.paint /
+oracle.readout — never with another GPU kernel.
 
 Integers (counts, bases, row tables) are compared exactly; positions
 and masses are moved, not computed, so they are compared bit for bit.
@@ -35,7 +35,7 @@ import sort_reference as ref                                    # noqa: E402
 from nbodykit_amd import hiplib                                 # noqa: E402
 from nbodykit_amd.source.mesh.catalog import (                  # noqa: E402
     _PAIR_GHOST, _two_level_ys, _pair_gs)
-from oracle import MeshGeometry, paint                          # noqa: E402
+from oracle import MeshGeometry, paint, readout                 # noqa: E402
 
 DEVICE = 'cuda'
 NBK_ERR_ARG = -2
@@ -622,6 +622,84 @@ def test_sorted_paint_edges_match_oracle(lib, mesh, cat, window, shift,
     got = run_scatter_paint(lib, lib.nbk_paint_sorted_f64, pos, mass,
                             nmesh, window, shift)
     assert_allclose(got, oracle_mesh(mesh, cat, window, shift),
+                    rtol=1e-12, atol=1e-12)
+
+
+# ---- (i) nbk_readout_f64 vs oracle.readout ------------------------------
+
+# 'nnb' (nearest grid point) exists for the readout only
+READOUT_IDS = dict(hiplib.WINDOW_IDS, nnb=3)
+
+
+@functools.lru_cache(maxsize=None)
+def readout_values(mesh):
+    values = numpy.random.RandomState(211).normal(size=MESHES[mesh])
+    values.setflags(write=False)
+    return values
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_readout(mesh, cat, window):
+    pos, _ = catalogue(mesh, cat)
+    want = readout(pos, readout_values(mesh),
+                   MeshGeometry(MESHES[mesh], BOX), resampler=window)
+    want.setflags(write=False)
+    return want
+
+
+def readout_comparable(pos, nmesh, window):
+    """Mask of the particles the oracle and the kernel must agree on.
+    The B-spline windows are continuous: all of them.  nnb is a step
+    function of the mesh coordinate, which the oracle computes as
+    x / H and the kernel as x * (N / L); where the two round to
+    different sides of a half-cell boundary they legitimately read
+    different cells, so those particles are left out — a condition on
+    the input, worked out from the two reference expressions alone."""
+    if window != 'nnb':
+        return numpy.ones(len(pos), dtype=bool)
+    N = numpy.asarray(nmesh, dtype='f8')
+    L = numpy.asarray(BOX, dtype='f8')
+    keep = (numpy.floor(pos * (N / L) + 0.5)
+            == numpy.floor(pos / (L / N) + 0.5)).all(axis=1)
+    assert (~keep).mean() <= 1.0 / 8
+    return keep
+
+
+def run_readout(lib, pos, values, nmesh, window, x0=0, nx=None):
+    nm, bx = geom_args(nmesh)
+    nx = nmesh[0] if nx is None else nx
+    pos_soa = dev(pos).t().contiguous()
+    values_t = dev(values[x0:x0 + nx])
+    out = nan_f64(len(pos))
+    hiplib.check(lib.nbk_readout_f64(
+        hiplib.dptr(pos_soa), len(pos), nm, bx, READOUT_IDS[window],
+        hiplib.dptr(values_t), x0, nx, hiplib.dptr(out), None), 'readout')
+    return host(out)
+
+
+@pytest.mark.parametrize('window', list(READOUT_IDS))
+@pytest.mark.parametrize('cat', list(ref.CATALOGUES))
+@pytest.mark.parametrize('mesh', list(MESHES))
+def test_readout_edges_match_oracle(lib, mesh, cat, window):
+    nmesh = MESHES[mesh]
+    pos, _ = catalogue(mesh, cat)
+    keep = readout_comparable(pos, nmesh, window)
+    got = run_readout(lib, pos, readout_values(mesh), nmesh, window)
+    assert_allclose(got[keep], oracle_readout(mesh, cat, window)[keep],
+                    rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize('window', list(READOUT_IDS))
+def test_readout_slab_halves(lib, window):
+    """each half of the mesh contributes its partial (cells outside the
+    slab read as 0); the partials sum to the full readout"""
+    nmesh = MESHES['thin8']
+    pos, _ = catalogue('thin8', 'edge')
+    keep = readout_comparable(pos, nmesh, window)
+    half = nmesh[0] // 2
+    got = sum(run_readout(lib, pos, readout_values('thin8'), nmesh, window,
+                          x0=x0, nx=half) for x0 in (0, half))
+    assert_allclose(got[keep], oracle_readout('thin8', 'edge', window)[keep],
                     rtol=1e-12, atol=1e-12)
 
 
