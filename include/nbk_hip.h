@@ -385,6 +385,79 @@ int nbk_fft_x_bin_f64(const double* data, const double* data2,
                       const int* ells, int nell,
                       double* out_sums, void* stream);
 
+/* pair counting --------------------------------------------------------
+ * Replaces Corrfunc.theory.DD / DDsmu / DDrppi as called from
+ * nbodykit/algorithms/pair_counters/corrfunc/theory.py (the compute core
+ * of SimulationBoxPairCount): a cell-list pair counter in f64 with no
+ * global atomics.
+ *
+ * Cell grid: cell (cx, cy, cz) of a particle is
+ * clamp(floor((p - origin) * inv_cell), 0, ncell - 1) per axis, flattened
+ * as (cx * ncell[1] + cy) * ncell[2] + cz; the caller picks a cell side
+ * >= the largest 3-D separation counted, and at most
+ * ncell[0]*ncell[1]*ncell[2] <= 40960 cells (one LDS histogram).
+ *
+ * Cell sort (same count-matrix scheme as nbk_xsort_*): with
+ * nchunks = ceil(n / chunk),
+ *   - nbk_pairs_cell_count_f64 writes one ncells-wide histogram row per
+ *     chunk into `mat` (nchunks x ncells, int32);
+ *   - nbk_scan_matrix_i32(mat, nchunks, ncells, ...) turns it into the
+ *     cursor seeds `bases` and the cell-start table bucket_bases
+ *     (ncells + 1, [ncells] = n);
+ *   - nbk_pairs_cell_scatter_f64 places the (n, 3) row-major positions
+ *     and the weights into SoA pos_out = x[n] y[n] z[n] and w_out[n],
+ *     ordered by cell (order within a cell is arbitrary).
+ * Requires n < 2^31.
+ */
+int nbk_pairs_cell_count_f64(const double* pos_aos, int64_t n, int chunk,
+                             const double origin[3],
+                             const double inv_cell[3], const int ncell[3],
+                             int* mat, void* stream);
+int nbk_pairs_cell_scatter_f64(const double* pos_aos, const double* weight,
+                               int64_t n, int chunk, const double origin[3],
+                               const double inv_cell[3], const int ncell[3],
+                               const int* bases, double* pos_out,
+                               double* w_out, void* stream);
+
+/* single-pass bin capacity of nbk_pairs_count_f64: nb0 * (j1 - j0) may
+ * not exceed it (three 8-byte LDS histograms per bin, 96 KiB) */
+#define NBK_PAIRS_MAX_BINS 4096
+int nbk_pairs_max_bins(void);
+
+/* Count the ordered pairs (i in catalogue 1, j in catalogue 2) of two
+ * cell-sorted SoA catalogues on the same cell grid.
+ *   mode 0 (DD):     bins of r;        q = (dx^2 + dy^2) + dz^2
+ *   mode 1 (DDsmu):  bins of (r, mu);  mu = |dz| / sqrt(q)
+ *   mode 2 (DDrppi): bins of (rp, pi); q = dx^2 + dy^2, pi = |dz|
+ * with d = (p1 - p2) - s * box per axis, s the periodic image (-1, 0, 1)
+ * of the neighbour cell; periodic = 0 visits in-range neighbours only.
+ * First-dimension bin k holds edges0_sq[k] <= q < edges0_sq[k+1]
+ * (edges0_sq: device, nb0 + 1 SQUARED edges); second-dimension bin j
+ * holds edges1[j] <= v < edges1[j+1] (device, nb1 + 1 edges; nb1 = 1 and
+ * edges1 ignored in mode 0), the last mu bin closed at its upper edge.
+ * Only second-dimension bins j0 <= j < j1 are counted by this call —
+ * requests above NBK_PAIRS_MAX_BINS run as several calls over disjoint
+ * slices.  autocorr = 1 (both sides the SAME arrays) skips the pairs
+ * whose two sorted indices are equal; both orderings are counted.
+ * The grid is `nblocks` persistent blocks striding over the cells;
+ * `partials` is scratch of 3 * nblocks * nb0 * (j1 - j0) 8-byte words
+ * (per-block histograms, plain stores), summed in block order into
+ *   npairs[nb0 * nb1] (int64), wsum (sum of w1 * w2), xsum (sum of r or
+ *   rp) at columns [j0, j1) — the other columns are left untouched.
+ * Integer counts are bitwise reproducible; the float sums are
+ * reproducible up to summation order. */
+int nbk_pairs_count_f64(const double* pos1, const double* w1,
+                        const int* start1, int64_t n1,
+                        const double* pos2, const double* w2,
+                        const int* start2, int64_t n2,
+                        int autocorr, const int ncell[3],
+                        const double box[3], int periodic,
+                        int mode, const double* edges0_sq, int nb0,
+                        const double* edges1, int nb1, int j0, int j1,
+                        int nblocks, void* partials,
+                        int64_t* npairs, double* wsum, double* xsum,
+                        void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

@@ -1,0 +1,534 @@
+// Cell-list pair counting (SimulationBoxPairCount): the replacement for
+// Corrfunc.theory.DD / DDsmu / DDrppi, f64 throughout.
+//
+// Pipeline (all launches on the caller's stream, NO global atomics):
+//  1. nbk_pairs_cell_count_f64 / nbk_scan_matrix_i32 /
+//     nbk_pairs_cell_scatter_f64: chunked counting sort by cell id (the
+//     count-matrix scheme of nbk_sort.hip: per-chunk LDS histograms, a
+//     device scan, LDS cursors) into SoA x[n] y[n] z[n] + w[n]; the
+//     scan's bucket_bases[ncells + 1] is the cell-start table.
+//  2. nbk_pairs_count_f64: a persistent grid strides over
+//     (first-catalogue cell, split) work items.  A block keeps up to
+//     blockDim first-catalogue particles in registers, walks the <= 27
+//     neighbour cells of the second catalogue, stages 256-particle tiles
+//     in LDS and bins every candidate into per-block LDS histograms
+//     (64-bit count, sum w1 w2, sum r) — then stores its partials with
+//     plain vector stores; a second kernel sums the partial rows in
+//     block order.
+//
+// Neighbour walk: per axis the offsets -1, 0, +1 map to
+// (cell, shift) = (c + d - s n, s) with s = floor((c + d) / n) for a
+// periodic axis, and are dropped when out of range otherwise.  The three
+// (cell, shift) pairs of an axis are distinct for EVERY n >= 1: with
+// n = 2 the offsets -1 and +1 alias the same cell but carry different
+// shifts (0 and -+1), with n = 1 all three alias cell 0 with shifts
+// -1, 0, +1.  A pair can be in range (|d - s L| < rmax <= L/2) under at
+// most one shift, so nothing is counted twice and nothing is missed.
+// The shift is applied as (x1 - x2) - s L, which for in-range pairs is
+// the same two roundings as the minimum-image expression
+// d = x1 - x2; d -= L if d > L/2; d += L if d < -L/2.
+//
+// Binning is on squared separations against squared first-dimension
+// edges (lower closed, upper open) and on mu = |dz| / r or pi = |dz|
+// against the published second-dimension edges; -ffp-contract=off keeps
+// every operation separately rounded, like numpy.
+#include "nbk_common.h"
+
+namespace {
+
+// tile of second-catalogue particles staged in LDS
+constexpr int PAIRS_TILE = 256;
+constexpr int PAIRS_THREADS = 256;
+
+struct PairsGrid {
+    double origin[3];
+    double inv_cell[3];
+    int ncell[3];
+};
+
+__device__ __forceinline__ int cell_axis(double x, double origin,
+                                         double inv_cell, int n) {
+    int c = (int)floor((x - origin) * inv_cell);
+    c = c < 0 ? 0 : c;
+    return c >= n ? n - 1 : c;
+}
+
+__device__ __forceinline__ int cell_of(double x, double y, double z,
+                                       const PairsGrid& g) {
+    const int cx = cell_axis(x, g.origin[0], g.inv_cell[0], g.ncell[0]);
+    const int cy = cell_axis(y, g.origin[1], g.inv_cell[1], g.ncell[1]);
+    const int cz = cell_axis(z, g.origin[2], g.inv_cell[2], g.ncell[2]);
+    return (cx * g.ncell[1] + cy) * g.ncell[2] + cz;
+}
+
+// ---- cell sort (count-matrix scheme, LDS histograms / cursors) --------
+__global__ void kpairs_cell_count(const double* __restrict__ pos, int64_t n,
+                                  int chunk, PairsGrid g, int ncells,
+                                  int* __restrict__ mat)
+{
+    extern __shared__ int hist[];   // ncells ints
+    for (int b = threadIdx.x; b < ncells; b += blockDim.x) hist[b] = 0;
+    __syncthreads();
+    const int64_t beg = (int64_t)blockIdx.x * chunk;
+    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
+    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x)
+        atomicAdd(&hist[cell_of(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2],
+                                g)], 1);
+    __syncthreads();
+    for (int b = threadIdx.x; b < ncells; b += blockDim.x)
+        mat[(int64_t)blockIdx.x * ncells + b] = hist[b];
+}
+
+__global__ void kpairs_cell_scatter(const double* __restrict__ pos,
+                                    const double* __restrict__ w, int64_t n,
+                                    int chunk, PairsGrid g, int ncells,
+                                    const int* __restrict__ bases,
+                                    double* __restrict__ ox,
+                                    double* __restrict__ oy,
+                                    double* __restrict__ oz,
+                                    double* __restrict__ ow)
+{
+    extern __shared__ int cur[];    // ncells running cursors
+    for (int b = threadIdx.x; b < ncells; b += blockDim.x)
+        cur[b] = bases[(int64_t)blockIdx.x * ncells + b];
+    __syncthreads();
+    const int64_t beg = (int64_t)blockIdx.x * chunk;
+    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
+    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
+        const double x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
+        const int64_t t = (int64_t)atomicAdd(&cur[cell_of(x, y, z, g)], 1);
+        ox[t] = x;
+        oy[t] = y;
+        oz[t] = z;
+        ow[t] = w[i];
+    }
+}
+
+// ---- pair count --------------------------------------------------------
+
+// index k of the bin with e[k] <= v < e[k + 1] over n + 1 ascending
+// edges; the caller has already checked e[0] <= v < e[n]
+__device__ __forceinline__ int bin_search(const double* e, int n, double v) {
+    int lo = 0, hi = n;             // invariant: e[lo] <= v < e[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (v >= e[mid]) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct PairsArgs {
+    const double* p1;  const double* w1;  const int* start1;  int64_t n1;
+    const double* p2;  const double* w2;  const int* start2;  int64_t n2;
+    int ncell[3];
+    int periodic;
+    double box[3];
+    int autocorr;
+    int nb0;            // first-dimension bins
+    int nb1;            // second-dimension bins (1 in 1d mode)
+    int j0, j1;         // slice [j0, j1) of the second dimension
+    int ncopy;          // histogram copies per block (waves share mod)
+    int split;          // work items per first-catalogue cell
+    const double* e0sq; // nb0 + 1 squared first-dimension edges
+    const double* e1;   // nb1 + 1 second-dimension edges (modes 1, 2)
+                        // — only the slice [j0, j1] is staged in LDS
+    unsigned long long* part_n;   // [gridDim.x * nb] partials
+    double* part_w;
+    double* part_x;
+};
+
+// one axis of the neighbour walk: offset d = -1, 0, +1 of cell c
+__device__ __forceinline__ bool neighbour_axis(int c, int d, int n,
+                                               int periodic, double L,
+                                               int* c2, double* shift) {
+    const int raw = c + d;
+    if (raw >= 0 && raw < n) {
+        *c2 = raw;
+        *shift = 0.0;
+        return true;
+    }
+    if (!periodic) return false;
+    if (raw < 0) {
+        *c2 = raw + n;
+        *shift = -L;
+    } else {
+        *c2 = raw - n;
+        *shift = L;
+    }
+    return true;
+}
+
+// MODE 0: 1d (r), 1: 2d (r, mu), 2: projected (rp, pi)
+template <int MODE>
+__global__ __launch_bounds__(PAIRS_THREADS)
+void kpairs_count(PairsArgs a)
+{
+    extern __shared__ __align__(16) double lds_f64[];
+    const int ns = a.j1 - a.j0;         // second-dimension bins this pass
+    const int nb = a.nb0 * ns;          // bins this pass
+    // layout: tile (xy, zw) | e0sq | e1 slice | count | wsum | xsum
+    double2* txy = reinterpret_cast<double2*>(lds_f64);
+    double2* tzw = txy + PAIRS_TILE;
+    double* e0sq = reinterpret_cast<double*>(tzw + PAIRS_TILE);
+    double* e1 = e0sq + (a.nb0 + 1);
+    unsigned long long* hn = reinterpret_cast<unsigned long long*>(
+        e1 + (MODE == 0 ? 0 : ns + 1));
+    double* hw = reinterpret_cast<double*>(hn + (size_t)a.ncopy * nb);
+    double* hx = hw + (size_t)a.ncopy * nb;
+
+    const int tid = threadIdx.x;
+    for (int k = tid; k <= a.nb0; k += blockDim.x) e0sq[k] = a.e0sq[k];
+    if (MODE != 0)
+        for (int k = tid; k <= ns; k += blockDim.x) e1[k] = a.e1[a.j0 + k];
+    for (int k = tid; k < a.ncopy * nb; k += blockDim.x) {
+        hn[k] = 0ull;
+        hw[k] = 0.0;
+        hx[k] = 0.0;
+    }
+    __syncthreads();
+
+    const double q_lo = e0sq[0], q_hi = e0sq[a.nb0];
+    // this pass's slice [v_lo, v_hi) of the second dimension; the last
+    // mu bin is closed at 1 (mu <= 1 always)
+    const double v_lo = (MODE == 0) ? 0.0 : e1[0];
+    const double v_hi = (MODE == 0) ? 0.0 : e1[ns];
+    const bool closed = (MODE == 1) && a.j1 == a.nb1;
+    const int copy = ((tid >> 6) % a.ncopy) * nb;
+    const int ncy = a.ncell[1], ncz = a.ncell[2];
+    const int ncells = a.ncell[0] * ncy * ncz;
+    const int64_t nitems = (int64_t)ncells * a.split;
+
+    const double* x1 = a.p1;
+    const double* y1 = a.p1 + a.n1;
+    const double* z1 = a.p1 + 2 * a.n1;
+    const double* x2 = a.p2;
+    const double* y2 = a.p2 + a.n2;
+    const double* z2 = a.p2 + 2 * a.n2;
+
+    for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const int c1 = (int)(item / a.split);
+        const int sp = (int)(item - (int64_t)c1 * a.split);
+        const int b1 = a.start1[c1], e1c = a.start1[c1 + 1];
+        const int cz = c1 % ncz;
+        const int cy = (c1 / ncz) % ncy;
+        const int cx = c1 / (ncz * ncy);
+
+        // every loop bound below is block-uniform: all threads reach
+        // every barrier, lanes without a particle only skip the binning
+        for (int ib = b1 + sp * PAIRS_THREADS; ib < e1c;
+             ib += a.split * PAIRS_THREADS) {
+            const int i = ib + tid;
+            const bool have = i < e1c;
+            const double xi = have ? x1[i] : 0.0;
+            const double yi = have ? y1[i] : 0.0;
+            const double zi = have ? z1[i] : 0.0;
+            const double wi = have ? a.w1[i] : 0.0;
+
+            for (int dxc = -1; dxc <= 1; dxc++) {
+                int nx;  double sx;
+                if (!neighbour_axis(cx, dxc, a.ncell[0], a.periodic,
+                                    a.box[0], &nx, &sx)) continue;
+                for (int dyc = -1; dyc <= 1; dyc++) {
+                    int ny;  double sy;
+                    if (!neighbour_axis(cy, dyc, ncy, a.periodic,
+                                        a.box[1], &ny, &sy)) continue;
+                    for (int dzc = -1; dzc <= 1; dzc++) {
+                        int nz;  double sz;
+                        if (!neighbour_axis(cz, dzc, ncz, a.periodic,
+                                            a.box[2], &nz, &sz)) continue;
+                        const int c2 = (nx * ncy + ny) * ncz + nz;
+                        const int b2 = a.start2[c2];
+                        const int e2 = a.start2[c2 + 1];
+
+                        for (int t0 = b2; t0 < e2; t0 += PAIRS_TILE) {
+                            const int nt = (e2 - t0 < PAIRS_TILE)
+                                         ? e2 - t0 : PAIRS_TILE;
+                            __syncthreads();    // previous tile consumed
+                            for (int t = tid; t < nt; t += blockDim.x) {
+                                txy[t] = make_double2(x2[t0 + t],
+                                                      y2[t0 + t]);
+                                tzw[t] = make_double2(z2[t0 + t],
+                                                      a.w2[t0 + t]);
+                            }
+                            __syncthreads();
+                            if (!have) continue;
+                            for (int t = 0; t < nt; t++) {
+                                const double2 pxy = txy[t];
+                                const double2 pzw = tzw[t];
+                                const double dx = (xi - pxy.x) - sx;
+                                const double dy = (yi - pxy.y) - sy;
+                                const double dz = (zi - pzw.x) - sz;
+                                const double rp2 = dx * dx + dy * dy;
+                                const double q = (MODE == 2)
+                                               ? rp2 : rp2 + dz * dz;
+                                if (!(q >= q_lo && q < q_hi)) continue;
+                                if (a.autocorr && t0 + t == i) continue;
+                                const double r = sqrt(q);
+                                int j = 0;
+                                if (MODE != 0) {
+                                    const double v = (MODE == 1)
+                                        ? fabs(dz) / r : fabs(dz);
+                                    if (v < v_lo) continue;
+                                    if (v < v_hi)
+                                        j = bin_search(e1, ns, v);
+                                    else if (closed)
+                                        j = ns - 1;
+                                    else
+                                        continue;
+                                }
+                                const int k = bin_search(e0sq, a.nb0, q);
+                                const int h = copy + k * ns + j;
+                                atomicAdd(&hn[h], 1ull);
+                                atomicAdd(&hw[h], wi * pzw.y);
+                                atomicAdd(&hx[h], r);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    __syncthreads();
+    // fold the copies in a fixed order and store this block's partials
+    for (int k = tid; k < nb; k += blockDim.x) {
+        unsigned long long cn = 0ull;
+        double cw = 0.0, cx_ = 0.0;
+        for (int c = 0; c < a.ncopy; c++) {
+            cn += hn[c * nb + k];
+            cw += hw[c * nb + k];
+            cx_ += hx[c * nb + k];
+        }
+        const size_t o = (size_t)blockIdx.x * nb + k;
+        a.part_n[o] = cn;
+        a.part_w[o] = cw;
+        a.part_x[o] = cx_;
+    }
+}
+
+// sums the [nblocks x nb] partial rows in block order into the
+// (nb0, nb1) outputs at second-dimension offset j0
+__global__ void kpairs_reduce(const unsigned long long* __restrict__ part_n,
+                              const double* __restrict__ part_w,
+                              const double* __restrict__ part_x,
+                              int nblocks, int nb0, int nb1, int j0, int j1,
+                              unsigned long long* __restrict__ out_n,
+                              double* __restrict__ out_w,
+                              double* __restrict__ out_x)
+{
+    const int ns = j1 - j0;
+    const int nb = nb0 * ns;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nb) return;
+    unsigned long long cn = 0ull;
+    double cw = 0.0, cx = 0.0;
+    for (int b = 0; b < nblocks; b++) {
+        cn += part_n[(size_t)b * nb + k];
+        cw += part_w[(size_t)b * nb + k];
+        cx += part_x[(size_t)b * nb + k];
+    }
+    const int o = (k / ns) * nb1 + j0 + (k % ns);
+    out_n[o] = cn;
+    out_w[o] = cw;
+    out_x[o] = cx;
+}
+
+// LDS ceiling of the cell-sort histograms, in ints (160 KiB)
+const int64_t PAIRS_MAX_CELLS = 40960;
+
+int make_grid(const double origin[3], const double inv_cell[3],
+              const int ncell[3], PairsGrid* g, const char* who)
+{
+    int64_t ncells = 1;
+    for (int i = 0; i < 3; i++) {
+        if (ncell[i] < 1) {
+            NBK_SET_ERR("%s: ncell[%d] = %d", who, i, ncell[i]);
+            return NBK_ERR_ARG;
+        }
+        g->origin[i] = origin[i];
+        g->inv_cell[i] = inv_cell[i];
+        g->ncell[i] = ncell[i];
+        ncells *= ncell[i];
+    }
+    if (ncells > PAIRS_MAX_CELLS) {
+        NBK_SET_ERR("%s: %lld cells exceed the %lld-cell LDS histogram",
+                    who, (long long)ncells, (long long)PAIRS_MAX_CELLS);
+        return NBK_ERR_ARG;
+    }
+    return NBK_OK;
+}
+
+void raise_lds(const void* fn, size_t bytes) {
+    if (bytes > 64 * 1024)
+        (void)hipFuncSetAttribute(fn,
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+size_t count_lds_bytes(int mode, int nb0, int ns, int ncopy) {
+    return (size_t)PAIRS_TILE * 2 * sizeof(double2)
+         + (size_t)(nb0 + 1) * sizeof(double)
+         + (mode == 0 ? 0 : (size_t)(ns + 1) * sizeof(double))
+         + (size_t)ncopy * nb0 * ns * 24;
+}
+
+}  // namespace
+
+extern "C" int nbk_pairs_cell_count_f64(const double* pos_aos, int64_t n,
+                                        int chunk, const double origin[3],
+                                        const double inv_cell[3],
+                                        const int ncell[3], int* mat,
+                                        void* stream)
+{
+    PairsGrid g;
+    const int rc = make_grid(origin, inv_cell, ncell, &g,
+                             "nbk_pairs_cell_count_f64");
+    if (rc != NBK_OK) return rc;
+    if (n < 0 || n >= ((int64_t)1 << 31) || chunk < 1) {
+        NBK_SET_ERR("nbk_pairs_cell_count_f64: n=%lld chunk=%d",
+                    (long long)n, chunk);
+        return NBK_ERR_ARG;
+    }
+    if (n == 0) return NBK_OK;
+    const int ncells = ncell[0] * ncell[1] * ncell[2];
+    const int64_t nblocks = (n + chunk - 1) / chunk;
+    const size_t lds = (size_t)ncells * sizeof(int);
+    raise_lds(reinterpret_cast<const void*>(&kpairs_cell_count), lds);
+    hipLaunchKernelGGL(kpairs_cell_count, dim3((uint32_t)nblocks),
+                       dim3(1024), lds, (hipStream_t)stream, pos_aos, n,
+                       chunk, g, ncells, mat);
+    NBK_CHECK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+extern "C" int nbk_pairs_cell_scatter_f64(const double* pos_aos,
+                                          const double* weight, int64_t n,
+                                          int chunk, const double origin[3],
+                                          const double inv_cell[3],
+                                          const int ncell[3],
+                                          const int* bases,
+                                          double* pos_out, double* w_out,
+                                          void* stream)
+{
+    PairsGrid g;
+    const int rc = make_grid(origin, inv_cell, ncell, &g,
+                             "nbk_pairs_cell_scatter_f64");
+    if (rc != NBK_OK) return rc;
+    if (n < 0 || n >= ((int64_t)1 << 31) || chunk < 1) {
+        NBK_SET_ERR("nbk_pairs_cell_scatter_f64: n=%lld chunk=%d",
+                    (long long)n, chunk);
+        return NBK_ERR_ARG;
+    }
+    if (n == 0) return NBK_OK;
+    const int ncells = ncell[0] * ncell[1] * ncell[2];
+    const int64_t nblocks = (n + chunk - 1) / chunk;
+    const size_t lds = (size_t)ncells * sizeof(int);
+    raise_lds(reinterpret_cast<const void*>(&kpairs_cell_scatter), lds);
+    hipLaunchKernelGGL(kpairs_cell_scatter, dim3((uint32_t)nblocks),
+                       dim3(1024), lds, (hipStream_t)stream, pos_aos,
+                       weight, n, chunk, g, ncells, bases, pos_out,
+                       pos_out + n, pos_out + 2 * n, w_out);
+    NBK_CHECK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+extern "C" int nbk_pairs_max_bins(void) { return NBK_PAIRS_MAX_BINS; }
+
+extern "C" int nbk_pairs_count_f64(const double* pos1, const double* w1,
+                                   const int* start1, int64_t n1,
+                                   const double* pos2, const double* w2,
+                                   const int* start2, int64_t n2,
+                                   int autocorr, const int ncell[3],
+                                   const double box[3], int periodic,
+                                   int mode, const double* edges0_sq,
+                                   int nb0, const double* edges1, int nb1,
+                                   int j0, int j1, int nblocks,
+                                   void* partials, int64_t* npairs,
+                                   double* wsum, double* xsum,
+                                   void* stream)
+{
+    const char* who = "nbk_pairs_count_f64";
+    if (mode < 0 || mode > 2 || nb0 < 1 || nb1 < 1
+        || (mode == 0 && nb1 != 1) || j0 < 0 || j1 > nb1 || j0 >= j1) {
+        NBK_SET_ERR("%s: bad mode/bins (mode=%d nb0=%d nb1=%d slice "
+                    "[%d, %d))", who, mode, nb0, nb1, j0, j1);
+        return NBK_ERR_ARG;
+    }
+    const int64_t nb = (int64_t)nb0 * (j1 - j0);
+    if (nb > NBK_PAIRS_MAX_BINS) {
+        NBK_SET_ERR("%s: %lld bins in one pass exceed the capacity %d",
+                    who, (long long)nb, NBK_PAIRS_MAX_BINS);
+        return NBK_ERR_ARG;
+    }
+    if (n1 < 0 || n2 < 0 || n1 >= ((int64_t)1 << 31)
+        || n2 >= ((int64_t)1 << 31) || nblocks < 1) {
+        NBK_SET_ERR("%s: n1=%lld n2=%lld nblocks=%d", who, (long long)n1,
+                    (long long)n2, nblocks);
+        return NBK_ERR_ARG;
+    }
+    int64_t ncells = 1;
+    for (int i = 0; i < 3; i++) {
+        if (ncell[i] < 1) {
+            NBK_SET_ERR("%s: ncell[%d] = %d", who, i, ncell[i]);
+            return NBK_ERR_ARG;
+        }
+        ncells *= ncell[i];
+    }
+    if (ncells > PAIRS_MAX_CELLS) {
+        NBK_SET_ERR("%s: too many cells (%lld)", who, (long long)ncells);
+        return NBK_ERR_ARG;
+    }
+    if (autocorr && (pos1 != pos2 || n1 != n2 || start1 != start2)) {
+        NBK_SET_ERR("%s: autocorr needs identical sorted inputs", who);
+        return NBK_ERR_ARG;
+    }
+
+    PairsArgs a;
+    a.p1 = pos1;  a.w1 = w1;  a.start1 = start1;  a.n1 = n1;
+    a.p2 = pos2;  a.w2 = w2;  a.start2 = start2;  a.n2 = n2;
+    for (int i = 0; i < 3; i++) {
+        a.ncell[i] = ncell[i];
+        a.box[i] = box[i];
+    }
+    a.periodic = periodic;
+    a.autocorr = autocorr;
+    a.nb0 = nb0;
+    a.nb1 = nb1;
+    a.j0 = j0;
+    a.j1 = j1;
+    // one histogram copy per wave while the copies stay within 48 KiB
+    // (so that two blocks stay resident per CU), fewer for more bins
+    a.ncopy = (nb * 24 * 4 <= 48 * 1024) ? 4
+            : (nb * 24 * 2 <= 48 * 1024) ? 2 : 1;
+    // enough work items for the grid when there are few cells
+    int64_t split = (4 * (int64_t)nblocks + ncells - 1) / ncells;
+    a.split = (int)(split < 1 ? 1 : (split > 64 ? 64 : split));
+    a.e0sq = edges0_sq;
+    a.e1 = edges1;
+    a.part_n = reinterpret_cast<unsigned long long*>(partials);
+    a.part_w = reinterpret_cast<double*>(partials) + (size_t)nblocks * nb;
+    a.part_x = a.part_w + (size_t)nblocks * nb;
+
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = count_lds_bytes(mode, nb0, j1 - j0, a.ncopy);
+    if (mode == 0) {
+        raise_lds(reinterpret_cast<const void*>(&kpairs_count<0>), lds);
+        hipLaunchKernelGGL(kpairs_count<0>, dim3((uint32_t)nblocks),
+                           dim3(PAIRS_THREADS), lds, s, a);
+    } else if (mode == 1) {
+        raise_lds(reinterpret_cast<const void*>(&kpairs_count<1>), lds);
+        hipLaunchKernelGGL(kpairs_count<1>, dim3((uint32_t)nblocks),
+                           dim3(PAIRS_THREADS), lds, s, a);
+    } else {
+        raise_lds(reinterpret_cast<const void*>(&kpairs_count<2>), lds);
+        hipLaunchKernelGGL(kpairs_count<2>, dim3((uint32_t)nblocks),
+                           dim3(PAIRS_THREADS), lds, s, a);
+    }
+    NBK_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kpairs_reduce, dim3((uint32_t)((nb + 255) / 256)),
+                       dim3(256), 0, s, a.part_n, a.part_w, a.part_x,
+                       nblocks, nb0, nb1, j0, j1,
+                       reinterpret_cast<unsigned long long*>(npairs),
+                       wsum, xsum);
+    NBK_CHECK_HIP(hipGetLastError());
+    return NBK_OK;
+}

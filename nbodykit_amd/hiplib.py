@@ -27,6 +27,8 @@ EXPORTED_SYMBOLS = [
     'nbk_compensate_f64', 'nbk_interlace_combine_f64', 'nbk_power3d_f64',
     'nbk_bin_power_f64', 'nbk_power_bin_f64', 'nbk_fft_x_bin_f64',
     'nbk_axpy_f64', 'nbk_scale_f64',
+    'nbk_pairs_cell_count_f64', 'nbk_pairs_cell_scatter_f64',
+    'nbk_pairs_max_bins', 'nbk_pairs_count_f64',
 ]
 
 _lib = None
@@ -158,6 +160,26 @@ def _declare(lib):
     lib.nbk_axpy_f64.argtypes = [c_void, c_void, c_f64, c_i64, c_void]
     lib.nbk_scale_f64.restype = ctypes.c_int
     lib.nbk_scale_f64.argtypes = [c_void, c_f64, ctypes.c_int, c_i64, c_void]
+    lib.nbk_pairs_cell_count_f64.restype = ctypes.c_int
+    lib.nbk_pairs_cell_count_f64.argtypes = [c_void, c_i64, ctypes.c_int,
+                                             c_f64_p, c_f64_p, c_int_p,
+                                             c_void, c_void]
+    lib.nbk_pairs_cell_scatter_f64.restype = ctypes.c_int
+    lib.nbk_pairs_cell_scatter_f64.argtypes = [c_void, c_void, c_i64,
+                                               ctypes.c_int, c_f64_p,
+                                               c_f64_p, c_int_p, c_void,
+                                               c_void, c_void, c_void]
+    lib.nbk_pairs_max_bins.restype = ctypes.c_int
+    lib.nbk_pairs_max_bins.argtypes = []
+    lib.nbk_pairs_count_f64.restype = ctypes.c_int
+    lib.nbk_pairs_count_f64.argtypes = [c_void, c_void, c_void, c_i64,
+                                        c_void, c_void, c_void, c_i64,
+                                        ctypes.c_int, c_int_p, c_f64_p,
+                                        ctypes.c_int, ctypes.c_int,
+                                        c_void, ctypes.c_int, c_void,
+                                        ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, c_void,
+                                        c_void, c_void, c_void, c_void]
 
 
 def load():
