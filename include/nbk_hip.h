@@ -435,6 +435,9 @@ int nbk_pairs_max_bins(void);
  * (edges0_sq: device, nb0 + 1 SQUARED edges); second-dimension bin j
  * holds edges1[j] <= v < edges1[j+1] (device, nb1 + 1 edges; nb1 = 1 and
  * edges1 ignored in mode 0), the last mu bin closed at its upper edge.
+ * A pair at zero separation (q = 0, reachable when edges0_sq[0] = 0) has
+ * no mu and is dropped in mode 1, whatever the slice; modes 0 and 2 count
+ * it (pi = 0).
  * Only second-dimension bins j0 <= j < j1 are counted by this call —
  * requests above NBK_PAIRS_MAX_BINS run as several calls over disjoint
  * slices.  autocorr = 1 (both sides the SAME arrays) skips the pairs

@@ -31,7 +31,9 @@
 // Binning is on squared separations against squared first-dimension
 // edges (lower closed, upper open) and on mu = |dz| / r or pi = |dz|
 // against the published second-dimension edges; -ffp-contract=off keeps
-// every operation separately rounded, like numpy.
+// every operation separately rounded, like numpy.  A pair at r = 0
+// (reachable when edges[0] = 0) has no mu and is dropped in mode 1; modes
+// 0 and 2 count it (q = 0, pi = 0).
 #include "nbk_common.h"
 
 namespace {
@@ -268,7 +270,10 @@ void kpairs_count(PairsArgs a)
                                 if (MODE != 0) {
                                     const double v = (MODE == 1)
                                         ? fabs(dz) / r : fabs(dz);
-                                    if (v < v_lo) continue;
+                                    // (also false for the NaN mu = 0/0
+                                    // of a pair at r = 0: it has no
+                                    // mu bin, in any pass)
+                                    if (!(v >= v_lo)) continue;
                                     if (v < v_hi)
                                         j = bin_search(e1, ns, v);
                                     else if (closed)

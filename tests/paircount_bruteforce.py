@@ -2,7 +2,8 @@
 Brute-force O(N1 N2) numpy oracle of the pair-counting contract
 (DESIGN.md "Pair counting"): every operation in f64, rounded separately,
 exactly as the expressions are written below.  Shared by
-test_paircount_cpu.py and test_gpu_paircount.py.
+test_paircount_cpu.py, test_gpu_paircount.py and
+test_gpu_pairs_kernels.py.
 """
 import numpy
 

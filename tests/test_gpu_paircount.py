@@ -14,7 +14,12 @@ Inputs: A = uniform_positions(3e-6, 512., seed 42 / 84) (395 / 355
 particles, the reference's own test catalogues), B =
 uniform_positions(2e-3, 100., seed 7 / 8) (1921 / 2058), weights
 RandomState(1).uniform(size=N), and the 8^3 lattice of spacing 8 in
-L = 64.
+L = 64.  From pairs_reference.py (the kernel-level tests' catalogues):
+SLAB, a thin anisotropic sheet far from the origin with a dense blob,
+PLANAR, the same flattened to zero extent in y, and the 10 x 9 x 8
+integer lattice LAT of the box (20, 18, 16) with its 40 doubled rows
+(LATDUP).  B1W is B1 with rows moved out of the box by -L and +2L and
+one row set to (L, 0, L), which the driver has to wrap.
 """
 import functools
 
@@ -29,6 +34,7 @@ if not torch.cuda.is_available():
     pytest.skip('no GPU', allow_module_level=True)
 
 import paircount_bruteforce as bf                               # noqa: E402
+import pairs_reference as pref                                  # noqa: E402
 from conftest import uniform_positions                          # noqa: E402
 from nbodykit_amd.lab import (ArrayCatalog, SimulationBoxPairCount,  # noqa
                               SimulationBox2PCF)
@@ -43,12 +49,23 @@ EDGES_B = numpy.linspace(1, 50, 15)
 EDGES_B2 = numpy.linspace(2, 40, 11)
 EDGES_B8 = numpy.geomspace(0.5, 12, 9)
 EDGES_LAT = [4, 8, 12, 16, 24, 32]
+EDGES_SLAB = numpy.linspace(1, 30, 8)
+EDGES_SLAB_P = numpy.linspace(1, 22, 8)
 
 
 @functools.lru_cache(maxsize=None)
 def positions(name):
     if name == 'lattice':
         pos, box = bf.lattice_positions(), 64.
+    elif name in ('SLAB', 'PLANAR'):
+        # non-periodic only: the box is required but has no use
+        pos, box = pref.catalogue(name)[0], 2048.
+    elif name == 'B1W':
+        b1, box = positions('B1')
+        pos = b1.copy()
+        pos[0::3] -= box
+        pos[1::3] += 2 * box
+        pos[2] = (box, 0., box)
     else:
         nbar, box, seed = {'A1': (3e-6, 512., 42), 'A2': (3e-6, 512., 84),
                            'B1': (2e-3, 100., 7),
@@ -97,6 +114,21 @@ def _cases():
         c['lattice_%s_2d' % tag] = ('lattice', None, EDGES_LAT, per,
                                     dict(Nmu=4))
     c['A_auto_empty_bin'] = ('A1', None, [0.01, 0.02, 150], True, {})
+    # anisotropic grids with a 1-cell axis and a cell above 256
+    # particles; los='y' moves the 1-cell axis
+    modes_s = [('1d', EDGES_SLAB, {}), ('2d', EDGES_SLAB, dict(Nmu=6)),
+               ('projected', EDGES_SLAB_P, dict(pimax=20))]
+    for tag, edges, kw in modes_s:
+        c['SLAB_nonperiodic_' + tag] = ('SLAB', None, edges, False, kw)
+        c['SLAB_nonperiodic_%s_y' % tag] = ('SLAB', None, edges, False,
+                                            dict(kw, los='y'))
+        # zero extent along y; in (r, mu) the margin is 5.8e-11, below
+        # the bar, so that mode is left out
+        if tag != '2d':
+            c['PLANAR_nonperiodic_' + tag] = ('PLANAR', None, edges, False,
+                                              kw)
+    # rows outside [0, L) (margins 1.8e-7, 1.8e-8)
+    c['B_wrapped_auto_2d'] = ('B1W', None, EDGES_B, True, dict(Nmu=7))
     return c
 
 
@@ -427,3 +459,86 @@ def test_save_load_roundtrip(tmp_path):
     assert_array_equal(t2.D1D2['npairs'], t.D1D2['npairs'])
     assert t2.D1R2 is None
     assert t2.attrs['pimax'] == 40
+
+
+# ---- gaps of the driver ------------------------------------------------
+
+def test_slab_grids_are_anisotropic():
+    """what the SLAB / PLANAR cases are there for"""
+    for name, los, ncell in [('SLAB_nonperiodic_2d', 'z', [9, 3, 1]),
+                             ('SLAB_nonperiodic_2d_y', 'y', [9, 1, 3]),
+                             ('SLAB_nonperiodic_projected', 'z', [10, 4, 1]),
+                             ('PLANAR_nonperiodic_1d', 'z', [9, 1, 1])]:
+        info = {}
+        orig = kernel.count_pairs
+        kernel.count_pairs = lambda *a, **k: orig(*a, info=info, **k)
+        try:
+            run_case(name)
+        finally:
+            kernel.count_pairs = orig
+        assert info['ncell'] == ncell, name
+        if name.startswith('SLAB'):
+            assert numpy.diff(info['start1']).max() > 256
+
+
+def test_wrapped_case_has_rows_outside_the_box():
+    """what B_wrapped_auto_2d (in test_pair_counts) is there for"""
+    pos, box = positions('B1W')
+    assert (pos < 0).any() and (pos > box).any() and (pos == box).any()
+    assert (pos.min(axis=0) < -0.9 * box).all()
+    assert (pos.max(axis=0) > 2.9 * box).all()
+
+
+@pytest.mark.parametrize('case', ['cross-copy', 'duplicated-rows'])
+def test_zero_separation_has_no_mu(case):
+    """edges[0] = 0 (which the class rejects, so through the driver): a
+    pair at r = 0 has mu = 0/0 and is dropped in '2d', as in the oracle;
+    LAT x a copy of LAT then equals LAT auto, and the 80 coincident
+    pairs of LATDUP are not counted."""
+    edges = numpy.array([0., 1, 2, 3, 5, 6, 7])
+    mu = bf.second_edges('2d', Nmu=5)
+    lat, _ = pref.catalogue('LAT')
+    first = pref.catalogue('LAT' if case == 'cross-copy' else 'LATDUP')[0]
+    w1 = weights(len(first))
+    second = w2 = None
+    if case == 'cross-copy':
+        second, w2 = lat.copy(), weights(len(lat))
+    with numpy.errstate(invalid='ignore', divide='ignore'):
+        want = bf.bruteforce_paircount('2d', first, edges, pref.LATBOX,
+                                       w1=w1, pos2=second, w2=w2, Nmu=5)
+    assert want['npairs'].sum() == (336804 if case == 'cross-copy'
+                                    else 376424)
+
+    def cols(pos, w):
+        return (torch.as_tensor(numpy.array(pos)).to('cuda'),
+                torch.as_tensor(w).to('cuda'))
+
+    pos1, w1_t = cols(first, w1)
+    pos2, w2_t = (None, None) if second is None else cols(second, w2)
+    npairs, wsum, xsum = kernel.count_pairs(
+        '2d', pos1, w1_t, pos2, w2_t, edges, mu, pref.LATBOX, True)
+    assert_array_equal(npairs, want['npairs'])
+    rtol = 4 * (want['npairs'].astype('f8') + 4) * EPS
+    assert (numpy.abs(wsum - want['wnpairs'])
+            <= rtol * want['wnpairs']).all()
+    full = npairs > 0
+    mean = numpy.zeros(xsum.shape)
+    mean[full] = xsum[full] / npairs[full]
+    assert (numpy.abs(mean - want['mean']) <= rtol * want['mean']).all()
+
+
+@pytest.mark.parametrize('periodic', [True, False])
+@pytest.mark.parametrize('mode,kw', [('1d', {}), ('2d', dict(Nmu=10)),
+                                     ('projected', dict(pimax=40))])
+def test_empty_second_catalogue(mode, kw, periodic):
+    empty = ArrayCatalog({'Position': numpy.zeros((0, 3)),
+                          'Weight': numpy.zeros(0)}, BoxSize=512.)
+    r = SimulationBoxPairCount(mode, catalog('A1'), EDGES_A, second=empty,
+                               periodic=periodic, **kw)
+    assert r.attrs['is_cross'] and r.attrs['N2'] == 0
+    assert r.attrs['total_wnpairs'] == 0.
+    assert r.pairs['npairs'].shape == ((9,) if mode == '1d' else
+                                       (9, 10) if mode == '2d' else (9, 40))
+    assert (r.pairs['npairs'] == 0).all()
+    assert (r.pairs['wnpairs'] == 0.).all()
+    assert (r.pairs[r.pairs.dims[0]] == 0.).all()

@@ -3,8 +3,9 @@ CPU coverage of the pair-counting feature: argument validation (which
 runs before the GPU is needed), the loud failure without a GPU, the
 weighted pair totals, the analytic-randoms filling factors, the natural
 and Landy-Szalay formulas, multipoles and wp of a constant wedge, JSON
-round-trips of synthetic results, the cell-grid picker and the
-brute-force oracle itself on the lattice.
+round-trips of synthetic results, the cell-grid picker, the
+brute-force oracle itself on the lattice, and the references, inputs and
+edge margins of the kernel-level tests (pairs_reference.py).
 """
 import warnings
 
@@ -13,6 +14,7 @@ import pytest
 from numpy.testing import assert_allclose, assert_array_equal
 
 import paircount_bruteforce as bf
+import pairs_reference as pref
 from nbodykit_amd.lab import (ArrayCatalog, UniformCatalog,
                               SimulationBoxPairCount, SimulationBox2PCF)
 from nbodykit_amd.algorithms.pair_counters import kernel, simbox
@@ -445,3 +447,205 @@ def test_bruteforce_lattice_hand_values():
     # non-periodic: the corner point has 3 neighbours at r = 8
     w3 = bf.bruteforce_paircount('1d', pos, edges, 64., periodic=False)
     assert w3['npairs'][1] == 2 * (3 * 7 * 64) + 2 * (3 * 2 * 49 * 8)
+
+
+# ---- the references of the kernel-level tests ----------------------------
+
+def test_cell_ids_hand_values():
+    """clamp(floor((p - origin) * inv_cell), 0, ncell - 1) per axis,
+    flattened (cx * ncy + cy) * ncz + cz, on a 4 x 3 x 2 grid of side
+    (2, 0.5, 8) at origin (-1, 10, 0)"""
+    origin, inv, ncell = [-1., 10., 0.], [0.5, 2., 0.125], [4, 3, 2]
+    up, down = numpy.inf, -numpy.inf
+    rows = [
+        ([-1., 10., 0.], (0, 0, 0)),                  # exactly at the origin
+        ([-1.5, 9., -3.], (0, 0, 0)),                 # below it: clamped
+        ([-100., -100., -100.], (0, 0, 0)),
+        ([numpy.nextafter(-1., down), 10., -0.0], (0, 0, 0)),
+        ([7., 11.5, 16.], (3, 2, 1)),                 # the top edge: clamped
+        ([numpy.nextafter(7., down), numpy.nextafter(11.5, down),
+          numpy.nextafter(16., down)], (3, 2, 1)),
+        ([7.5, 12., 1e3], (3, 2, 1)),                 # above it
+        ([1., 10.5, 8.], (1, 1, 1)),                  # interior boundaries
+        # just below them; in x the subtraction (1 - 2^-53) + 1 rounds
+        # up to 2 and the row belongs to cell 1, in y and z it is exact
+        ([numpy.nextafter(1., down), numpy.nextafter(10.5, down),
+          numpy.nextafter(8., down)], (1, 0, 0)),
+        ([numpy.nextafter(1., up), numpy.nextafter(10.5, up),
+          numpy.nextafter(8., up)], (1, 1, 1)),
+        ([0.0, 11., 0.0], (0, 2, 0)),
+        ([-0.0, 11., -0.0], (0, 2, 0)),
+        ([5., 10.75, 4.], (3, 1, 0)),
+    ]
+    pos = numpy.array([r[0] for r in rows])
+    want = [(cx * 3 + cy) * 2 + cz for _, (cx, cy, cz) in rows]
+    assert_array_equal(pref.cell_ids(pos, origin, inv, ncell), want)
+    # a flat axis (inv_cell = 0) is one cell whatever the coordinate
+    flat = pref.cell_ids(pos, origin, [0.5, 0., 0.125], [4, 1, 2])
+    assert_array_equal(flat, [cx * 2 + cz for _, (cx, _cy, cz) in rows])
+    # anisotropic flattening: the id of a cell is not symmetric in y, z
+    assert pref.cell_ids([[-1., 10.5, 0.]], origin, inv, ncell)[0] == 2
+    assert pref.cell_ids([[-1., 10., 8.]], origin, inv, ncell)[0] == 1
+
+
+def test_sorted_reference_and_clamp_rows():
+    origin, inv, ncell = [-1., 10., 0.], [0.5, 2., 0.125], [4, 3, 2]
+    pos = pref.clamp_rows(origin, inv, ncell, n=500)
+    w = pref.weights(len(pos))
+    ids = pref.cell_ids(pos, origin, inv, ncell)
+    # the hand-placed rows reach every cell of the corner cases
+    assert set([0, 23]) <= set(ids) and ids.min() >= 0 and ids.max() < 24
+    for ax, (lo, top) in enumerate([(-1., 7.), (10., 11.5), (0., 16.)]):
+        x = pos[:, ax]
+        for v in (lo, top, 0.0):
+            assert (x == v).any()
+        assert (x < lo).any() and (x > top).any()
+        assert (x == numpy.nextafter(lo, -numpy.inf)).any()
+        assert (x == numpy.nextafter(top, -numpy.inf)).any()
+        assert numpy.signbit(x[x == 0]).any()
+    start, rows = pref.sorted_reference(pos, w, ids, 24)
+    assert start[0] == 0 and start[-1] == len(pos)
+    assert_array_equal(numpy.diff(start), numpy.bincount(ids, minlength=24))
+    # a stable sort by cell holds the same canonical rows; a swapped
+    # weight inside one cell does not
+    order = numpy.argsort(ids, kind='stable')
+    keys = pref.sorted_keys(start)
+    assert_array_equal(keys, ids[order])
+    assert_array_equal(pref.canonical_rows(pos[order], w[order], keys),
+                       rows)
+    cell = numpy.flatnonzero(numpy.diff(start) >= 2)[0]
+    wrong = w[order].copy()
+    a = start[cell]
+    wrong[[a, a + 1]] = wrong[[a + 1, a]]
+    assert not numpy.array_equal(
+        pref.canonical_rows(pos[order], wrong, keys), rows)
+    # chunk histograms and their scan
+    mat = pref.chunk_histograms(ids, 24, 120)
+    assert mat.shape == (5, 24) and mat[-1].sum() == 20
+    bases, start2 = pref.scan_matrix(mat)
+    assert_array_equal(start2, start)
+    assert_array_equal(bases[0], start[:-1])
+    assert_array_equal(bases[-1] + mat[-1], start[1:])
+
+
+# (first, second, mode, edges, keywords, box, periodic) -> the margins
+# measured for the kernel-level cases: (r^2 relative, second dimension
+# absolute), to two digits
+H_EDGES = numpy.linspace(0.5, 18, 8)
+HP_EDGES = numpy.linspace(0.5, 14, 7)
+S_EDGES = numpy.linspace(1, 30, 8)
+SP_EDGES = numpy.linspace(1, 22, 8)
+MARGIN_TABLE = {
+    'H1 auto 1d': ('H1', None, '1d', H_EDGES, {}, 1.2e-6, None),
+    'H1 auto 2d': ('H1', None, '2d', H_EDGES, dict(Nmu=10), 1.2e-6,
+                   4.2e-7),
+    'H1xH2 1d': ('H1', 'H2', '1d', H_EDGES, {}, 2.1e-8, None),
+    'H1xH2 2d': ('H1', 'H2', '2d', H_EDGES, dict(Nmu=10), 2.1e-8, 1.1e-7),
+    'H1 auto projected': ('H1', None, 'projected', HP_EDGES,
+                          dict(pimax=12), 1.4e-6, 1.6e-6),
+    'H1xH2 projected': ('H1', 'H2', 'projected', HP_EDGES, dict(pimax=12),
+                        2.4e-7, 6.7e-6),
+    'SLAB 1d': ('SLAB', None, '1d', S_EDGES, {}, 1.1e-6, None),
+    'SLAB 2d': ('SLAB', None, '2d', S_EDGES, dict(Nmu=6), 1.1e-6, 5.2e-7),
+    'SLAB projected': ('SLAB', None, 'projected', SP_EDGES, dict(pimax=20),
+                       7.9e-6, 1.8e-6),
+    'PLANAR 1d': ('PLANAR', None, '1d', S_EDGES, {}, 6.2e-7, None),
+    'PLANAR projected': ('PLANAR', None, 'projected', SP_EDGES,
+                         dict(pimax=20), 4.4e-7, 1.8e-6),
+}
+
+
+@pytest.mark.parametrize('case', sorted(MARGIN_TABLE))
+def test_kernel_case_margins(case):
+    """exact npairs in test_gpu_pairs_kernels.py rests on these: no pair
+    within 1e-10 of a bin edge, none at mu = 1"""
+    first, second, mode, edges, kw, m0, m1 = MARGIN_TABLE[case]
+    pos1, w1 = pref.catalogue(first)
+    pos2 = w2 = None
+    if second is not None:
+        pos2, w2 = pref.catalogue(second)
+    periodic = first.startswith('H')
+    want = bf.bruteforce_paircount(
+        mode, pos1, edges, pref.HBOX if periodic else 0., w1=w1, pos2=pos2,
+        w2=w2, periodic=periodic, **kw)
+    assert want['margin0'] > 1e-10 and want['margin1'] > 1e-10
+    assert want['n_mu1'] == 0
+    assert_allclose(want['margin0'], m0, rtol=0.05)
+    if m1 is None:
+        assert want['margin1'] == numpy.inf
+    else:
+        assert_allclose(want['margin1'], m1, rtol=0.05)
+
+
+def test_planar_mu_margin_is_below_the_bar():
+    """why PLANAR has no (r, mu) case: in a plane that contains the line
+    of sight mu crowds against 1"""
+    pos, w = pref.catalogue('PLANAR')
+    want = bf.bruteforce_paircount('2d', pos, S_EDGES, 0., w1=w,
+                                   periodic=False, Nmu=6)
+    assert 0 < want['margin1'] < 1e-10
+
+
+@pytest.mark.parametrize('Nmu', [10, 100, 200, 512])
+def test_copies_case_margins(Nmu):
+    pos, w = pref.catalogue('H1')
+    want = bf.bruteforce_paircount('2d', pos, numpy.linspace(0.5, 18, 9),
+                                   pref.HBOX, w1=w, Nmu=Nmu)
+    assert want['margin0'] > 1e-10 and want['margin1'] > 1e-10
+    assert want['n_mu1'] == 0
+
+
+def test_lattice_zero_separation_facts():
+    """10 x 9 x 8 integer lattice in the periodic box (20, 18, 16),
+    edges[0] = 0: a pair at r = 0 is counted in 1d and projected
+    (q = 0 >= 0, pi = 0) and dropped in 2d, where mu = 0/0 has no bin"""
+    lat, _ = pref.catalogue('LAT')
+    dup, _ = pref.catalogue('LATDUP')
+    assert lat.shape == (720, 3) and dup.shape == (760, 3)
+    edges = [0, 1, 2, 3, 5, 6, 7]
+    totals = {}
+    for mode, kw in [('1d', {}), ('2d', dict(Nmu=5)),
+                     ('projected', dict(pimax=4))]:
+        with numpy.errstate(invalid='ignore', divide='ignore'):
+            auto = bf.bruteforce_paircount(mode, lat, edges, pref.LATBOX,
+                                           **kw)
+            cross = bf.bruteforce_paircount(mode, lat, edges, pref.LATBOX,
+                                            pos2=lat.copy(), **kw)
+            both = bf.bruteforce_paircount(mode, dup, edges, pref.LATBOX,
+                                           **kw)
+        totals[mode] = [int(r['npairs'].sum())
+                        for r in (auto, cross, both)]
+        diff = cross['npairs'].astype('i8') - auto['npairs'].astype('i8')
+        if mode == '2d':
+            assert not diff.any()
+            assert auto['n_mu1'] == 4860
+        else:
+            # all of them in the very first bin
+            assert diff.ravel()[0] == 720 and diff.sum() == 720
+    assert totals['1d'][:2] == [336804, 336804 + 720]
+    assert totals['2d'][:2] == [336804, 336804]
+    assert totals['projected'][1] - totals['projected'][0] == 720
+    assert totals['1d'][2] == 376504 and totals['2d'][2] == 376424
+    # mu = 3/5 sits one ulp below the published edge
+    assert numpy.linspace(0, 1., 6)[3] == numpy.nextafter(0.6, 1.) > 3. / 5
+
+
+def test_slab_grid_is_anisotropic():
+    """extents 298.8 x 119.8 x 34.8: floor(extent / 30) = (9, 3, 1), and
+    (10, 4, 1) for the projected reach sqrt(22^2 + 20^2) = 29.73"""
+    lo, hi = pref.bounding_box('SLAB')
+    assert_allclose(hi - lo, [298.788, 119.766, 34.763], atol=1e-3)
+    origin, inv, ncell = kernel.make_grid(False, None, 30., lo, hi)
+    assert ncell == [9, 3, 1]
+    assert_array_equal(origin, lo)
+    assert_allclose(inv, numpy.array(ncell) / (hi - lo), rtol=1e-15)
+    rmax = kernel.max_3d_separation('projected', SP_EDGES, 20)
+    assert kernel.make_grid(False, None, rmax, lo, hi)[2] == [10, 4, 1]
+    # the blob: one cell holds more than a 256-particle tile
+    pos, _ = pref.catalogue('SLAB')
+    ids = pref.cell_ids(pos, origin, inv, ncell)
+    assert numpy.bincount(ids, minlength=27).max() > 256
+    # flattened: a single cell of zero extent along y
+    lo, hi = pref.bounding_box('PLANAR')
+    origin, inv, ncell = kernel.make_grid(False, None, 30., lo, hi)
+    assert ncell == [9, 1, 1] and inv[1] == 0. and origin[1] == 3.25
