@@ -165,54 +165,42 @@ int nbk_bucket_scatter_f64(const double* pos_aos, const double* mass,
                            double* pos_out, double* mass_out,
                            void* stream);
 
-/* Two-level atomic-free cell sort (the paint locality pass for big
- * meshes).  The GPU's global-atomic pipe runs at ~25 G ops/s regardless
- * of locality (csrc/count_probe.hip), so the single-level
- * count/scatter above is atomic-bound at 1e9 particles; this pipeline
- * keeps every histogram/cursor in LDS:
+/* Count-matrix sorts (the paint locality passes for big meshes).  The
+ * GPU's global-atomic pipe runs at ~25 G ops/s regardless of locality
+ * (csrc/count_probe.hip), so the single-level count/scatter above is
+ * atomic-bound at 1e9 particles; these pipelines keep every
+ * histogram/cursor in LDS.  They share one scheme (csrc/nbk_countsort.h;
+ * nbk_pairs_cell_* below is its third key): a *_count step writes one
+ * nbuckets-wide histogram row per chunk of `chunk` particles into `mat`
+ * (ceil(n/chunk) x nbuckets, int32 row-major), nbk_scan_matrix_i32 scans
+ * it, and a *_scatter step re-reads each chunk and places SoA planes
+ * from LDS cursors (deterministic bucket ranges, arbitrary order within
+ * a bucket).  Every step requires 0 <= n < 2^31, chunk >= 1 (the same
+ * chunk in both steps) and 1 <= nbuckets <= 40960 (160 KiB of LDS ints),
+ * checks its geometry whatever n is, returns NBK_ERR_ARG before
+ * launching anything otherwise, and does nothing for n = 0.
  *
- *  coarse key = ix * (n1>>ys) + (iy>>ys), ys chosen so that BOTH
- *  nbuckets = n0*(n1>>ys) and the fine window (1<<ys)*n2 are <= 40960
- *  ints (160 KiB LDS):
- *   - nbk_xsort_count_f64 (pass A): one nbuckets-wide histogram row per
- *     chunk of `chunk` particles into `mat` (ceil(n/chunk) x nbuckets,
- *     int32 row-major), plus the cell-order detection into
- *     scrambled_flag (may be NULL);
- *   - nbk_scan_matrix_i32: device scan of `mat` -> per-chunk cursor
- *     seeds `bases` (chunk-major) and bucket edges `bucket_bases`
- *     (nbuckets+1, exclusive; [nbuckets] = n).  colsum_tmp is
- *     9 * nbuckets ints of scratch (8 segment partials + column sums);
- *   - nbk_xsort_scatter_f64 (pass C): re-reads each chunk, places SoA
- *     planes (x[n] y[n] z[n] into pos_out) from LDS cursors seeded
- *     with `bases` (deterministic — no global atomics);
- *   - nbk_bucket_fine_f64: one block per coarse bucket over the SoA
- *     coarse output; counts the bucket's cells in an LDS window,
- *     block-scans it, and emits the exact cell-sorted SoA output
- *     (x[n] y[n] z[n]) — no global atomics.
+ * nbk_scan_matrix_i32: device scan of `mat` -> per-chunk cursor seeds
+ * `bases` (chunk-major) and bucket edges `bucket_bases` (nbuckets+1,
+ * exclusive; [nbuckets] = the number of placed particles).  colsum_tmp
+ * is 9 * nbuckets ints of scratch (8 segment partials + column sums). */
+int nbk_scan_matrix_i32(const int* mat, int64_t nblocks, int64_t nbuck,
+                        int* colsum_tmp, int* bases, int* bucket_bases,
+                        void* stream);
+
+/* Two-level cell sort: coarse key = ix * (n1>>ys) + (iy>>ys), ys chosen
+ * so that BOTH nbuckets = n0*(n1>>ys) and the fine window (1<<ys)*n2 fit
+ * the LDS.  nbk_xsort_count_f64 (pass A) also detects cell-ordered input
+ * into scrambled_flag (may be NULL); nbk_xsort_scatter_f64 (pass C)
+ * writes x[n] y[n] z[n] into pos_out (mass may be NULL);
+ * nbk_bucket_fine_f64 runs one block per coarse bucket over that SoA
+ * output: it counts the bucket's cells in an LDS window, block-scans it,
+ * and emits the exact cell-sorted SoA output — no global atomics.
  * Requires power-friendly dims (n1 divisible by 1<<ys, window
- * divisible by 1024) and n < 2^31. */
+ * divisible by 1024). */
 int nbk_xsort_count_f64(const double* pos_aos, int64_t n, int chunk,
                         const int64_t nmesh[3], const double box[3],
                         int ys, int* mat, int* scrambled_flag,
-                        void* stream);
-/* PAIR-BUCKET duplicating sort (see nbk_paint_gather_f64 pair_gs):
- * counting sort by (x-plane pair, y row-group) with each particle
- * duplicated into every y-group rows [iy+dlo, iy+dhi] of its deposit
- * stencil touch (<= 2 copies; dhi-dlo must be < 1<<ys).  Same
- * count-matrix/scan/scatter structure as nbk_xsort_*; n_out =
- * bucket_bases[nbuck] after nbk_scan_matrix_i32. */
-int nbk_psort_count_f64(const double* pos_aos, int64_t n, int chunk,
-                        const int64_t nmesh[3], const double box[3],
-                        int ys, int dlo, int dhi, int* mat, void* stream);
-int nbk_psort_scatter_f64(const double* pos_aos, const double* mass,
-                          int64_t n, int chunk, const int64_t nmesh[3],
-                          const double box[3], int ys, int dlo, int dhi,
-                          const int* bases, int64_t n_out,
-                          double* pos_out, double* mass_out,
-                          void* stream);
-
-int nbk_scan_matrix_i32(const int* mat, int64_t nblocks, int64_t nbuck,
-                        int* colsum_tmp, int* bases, int* bucket_bases,
                         void* stream);
 int nbk_xsort_scatter_f64(const double* pos_aos, const double* mass,
                           int64_t n, int chunk, const int64_t nmesh[3],
@@ -225,6 +213,23 @@ int nbk_bucket_fine_f64(const double* pos_soa, const double* mass,
                         const int* bucket_bases,
                         double* soa_out, double* mass_out,
                         int* rowtab, int rows_only, void* stream);
+
+/* PAIR-BUCKET duplicating sort (see nbk_paint_gather_f64 pair_gs):
+ * key = (x-plane pair, y row-group) with each particle duplicated into
+ * every y-group rows [iy+dlo, iy+dhi] of its deposit stencil touch
+ * (<= 2 copies).  Both steps require n0 even, n1 divisible by 1<<ys and
+ * dhi-dlo < 1<<ys; n_out = bucket_bases[nbuck] after
+ * nbk_scan_matrix_i32, and the output planes are x[n_out] y[n_out]
+ * z[n_out]. */
+int nbk_psort_count_f64(const double* pos_aos, int64_t n, int chunk,
+                        const int64_t nmesh[3], const double box[3],
+                        int ys, int dlo, int dhi, int* mat, void* stream);
+int nbk_psort_scatter_f64(const double* pos_aos, const double* mass,
+                          int64_t n, int chunk, const int64_t nmesh[3],
+                          const double box[3], int ys, int dlo, int dhi,
+                          const int* bases, int64_t n_out,
+                          double* pos_out, double* mass_out,
+                          void* stream);
 
 /* readout (gather dual of paint; window 0/1/2 = cic/tsc/pcs, 3 = nnb).
  * Serves FFTRecon's displacement solve (fftrecon.py:246-249) and the
@@ -397,8 +402,8 @@ int nbk_fft_x_bin_f64(const double* data, const double* data2,
  * >= the largest 3-D separation counted, and at most
  * ncell[0]*ncell[1]*ncell[2] <= 40960 cells (one LDS histogram).
  *
- * Cell sort (same count-matrix scheme as nbk_xsort_*): with
- * nchunks = ceil(n / chunk),
+ * Cell sort (the count-matrix scheme of nbk_xsort_*, with its n / chunk
+ * requirements): with nchunks = ceil(n / chunk),
  *   - nbk_pairs_cell_count_f64 writes one ncells-wide histogram row per
  *     chunk into `mat` (nchunks x ncells, int32);
  *   - nbk_scan_matrix_i32(mat, nchunks, ncells, ...) turns it into the
@@ -407,7 +412,6 @@ int nbk_fft_x_bin_f64(const double* data, const double* data2,
  *   - nbk_pairs_cell_scatter_f64 places the (n, 3) row-major positions
  *     and the weights into SoA pos_out = x[n] y[n] z[n] and w_out[n],
  *     ordered by cell (order within a cell is arbitrary).
- * Requires n < 2^31.
  */
 int nbk_pairs_cell_count_f64(const double* pos_aos, int64_t n, int chunk,
                              const double origin[3],

@@ -12,9 +12,11 @@ from nbodykit_amd import hiplib, profiling
 
 MODE_IDS = {'1d': 0, '2d': 1, 'projected': 2}
 
-# cells per axis: 34^3 = 39304 fits the 40960-int LDS histogram of the
+# cells per axis: the largest cube that fits the LDS histogram of the
 # cell sort
 MAX_CELLS_PER_AXIS = 34
+assert MAX_CELLS_PER_AXIS ** 3 <= hiplib.SORT_LDS_INTS \
+    < (MAX_CELLS_PER_AXIS + 1) ** 3
 
 
 def max_3d_separation(mode, edges, pimax):
@@ -133,12 +135,8 @@ def cell_sort(lib, pos, w, origin, inv_cell, ncell):
     hiplib.check(lib.nbk_pairs_cell_count_f64(
         hiplib.dptr(pos), n, chunk, origin_c, inv_c, ncell_c,
         hiplib.dptr(mat), stream), 'nbk_pairs_cell_count_f64')
-    colsum = torch.empty(9 * ncells, dtype=torch.int32, device='cuda')
-    bases = torch.empty(nchunks * ncells, dtype=torch.int32, device='cuda')
-    hiplib.check(lib.nbk_scan_matrix_i32(
-        hiplib.dptr(mat), nchunks, ncells, hiplib.dptr(colsum),
-        hiplib.dptr(bases), hiplib.dptr(start), stream),
-        'nbk_scan_matrix_i32')
+    bases, _ = hiplib.scan_count_matrix(lib, mat, nchunks, ncells, stream,
+                                        bucket_bases=start)
     hiplib.check(lib.nbk_pairs_cell_scatter_f64(
         hiplib.dptr(pos), hiplib.dptr(w), n, chunk, origin_c, inv_c,
         ncell_c, hiplib.dptr(bases), hiplib.dptr(out), hiplib.dptr(out_w),

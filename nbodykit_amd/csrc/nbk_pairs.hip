@@ -3,10 +3,10 @@
 //
 // Pipeline (all launches on the caller's stream, NO global atomics):
 //  1. nbk_pairs_cell_count_f64 / nbk_scan_matrix_i32 /
-//     nbk_pairs_cell_scatter_f64: chunked counting sort by cell id (the
-//     count-matrix scheme of nbk_sort.hip: per-chunk LDS histograms, a
-//     device scan, LDS cursors) into SoA x[n] y[n] z[n] + w[n]; the
-//     scan's bucket_bases[ncells + 1] is the cell-start table.
+//     nbk_pairs_cell_scatter_f64: the count-matrix sort of
+//     nbk_countsort.h with the cell id as its key, into SoA
+//     x[n] y[n] z[n] + w[n]; the scan's bucket_bases[ncells + 1] is the
+//     cell-start table.
 //  2. nbk_pairs_count_f64: a persistent grid strides over
 //     (first-catalogue cell, split) work items.  A block keeps up to
 //     blockDim first-catalogue particles in registers, walks the <= 27
@@ -34,19 +34,13 @@
 // every operation separately rounded, like numpy.  A pair at r = 0
 // (reachable when edges[0] = 0) has no mu and is dropped in mode 1; modes
 // 0 and 2 count it (q = 0, pi = 0).
-#include "nbk_common.h"
+#include "nbk_countsort.h"
 
 namespace {
 
 // tile of second-catalogue particles staged in LDS
 constexpr int PAIRS_TILE = 256;
 constexpr int PAIRS_THREADS = 256;
-
-struct PairsGrid {
-    double origin[3];
-    double inv_cell[3];
-    int ncell[3];
-};
 
 __device__ __forceinline__ int cell_axis(double x, double origin,
                                          double inv_cell, int n) {
@@ -55,56 +49,22 @@ __device__ __forceinline__ int cell_axis(double x, double origin,
     return c >= n ? n - 1 : c;
 }
 
-__device__ __forceinline__ int cell_of(double x, double y, double z,
-                                       const PairsGrid& g) {
-    const int cx = cell_axis(x, g.origin[0], g.inv_cell[0], g.ncell[0]);
-    const int cy = cell_axis(y, g.origin[1], g.inv_cell[1], g.ncell[1]);
-    const int cz = cell_axis(z, g.origin[2], g.inv_cell[2], g.ncell[2]);
-    return (cx * g.ncell[1] + cy) * g.ncell[2] + cz;
-}
+// the cell sort's key: the clamped cell id
+struct PairsCellKey {
+    typedef int index_t;
+    static constexpr bool two_keys = false;
+    double origin[3];
+    double inv_cell[3];
+    int ncell[3];
 
-// ---- cell sort (count-matrix scheme, LDS histograms / cursors) --------
-__global__ void kpairs_cell_count(const double* __restrict__ pos, int64_t n,
-                                  int chunk, PairsGrid g, int ncells,
-                                  int* __restrict__ mat)
-{
-    extern __shared__ int hist[];   // ncells ints
-    for (int b = threadIdx.x; b < ncells; b += blockDim.x) hist[b] = 0;
-    __syncthreads();
-    const int64_t beg = (int64_t)blockIdx.x * chunk;
-    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
-    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x)
-        atomicAdd(&hist[cell_of(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2],
-                                g)], 1);
-    __syncthreads();
-    for (int b = threadIdx.x; b < ncells; b += blockDim.x)
-        mat[(int64_t)blockIdx.x * ncells + b] = hist[b];
-}
-
-__global__ void kpairs_cell_scatter(const double* __restrict__ pos,
-                                    const double* __restrict__ w, int64_t n,
-                                    int chunk, PairsGrid g, int ncells,
-                                    const int* __restrict__ bases,
-                                    double* __restrict__ ox,
-                                    double* __restrict__ oy,
-                                    double* __restrict__ oz,
-                                    double* __restrict__ ow)
-{
-    extern __shared__ int cur[];    // ncells running cursors
-    for (int b = threadIdx.x; b < ncells; b += blockDim.x)
-        cur[b] = bases[(int64_t)blockIdx.x * ncells + b];
-    __syncthreads();
-    const int64_t beg = (int64_t)blockIdx.x * chunk;
-    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
-    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const double x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
-        const int64_t t = (int64_t)atomicAdd(&cur[cell_of(x, y, z, g)], 1);
-        ox[t] = x;
-        oy[t] = y;
-        oz[t] = z;
-        ow[t] = w[i];
+    __device__ __forceinline__ int operator()(double x, double y,
+                                              double z) const {
+        const int cx = cell_axis(x, origin[0], inv_cell[0], ncell[0]);
+        const int cy = cell_axis(y, origin[1], inv_cell[1], ncell[1]);
+        const int cz = cell_axis(z, origin[2], inv_cell[2], ncell[2]);
+        return (cx * ncell[1] + cy) * ncell[2] + cz;
     }
-}
+};
 
 // ---- pair count --------------------------------------------------------
 
@@ -338,13 +298,12 @@ __global__ void kpairs_reduce(const unsigned long long* __restrict__ part_n,
     out_x[o] = cx;
 }
 
-// LDS ceiling of the cell-sort histograms, in ints (160 KiB)
-const int64_t PAIRS_MAX_CELLS = 40960;
-
-int make_grid(const double origin[3], const double inv_cell[3],
-              const int ncell[3], PairsGrid* g, const char* who)
+// grid checks + key of nbk_pairs_cell_*; `who` names the entry point
+int make_grid(const char* who, const double origin[3],
+              const double inv_cell[3], const int ncell[3],
+              PairsCellKey* g, int64_t* ncells)
 {
-    int64_t ncells = 1;
+    *ncells = 1;
     for (int i = 0; i < 3; i++) {
         if (ncell[i] < 1) {
             NBK_SET_ERR("%s: ncell[%d] = %d", who, i, ncell[i]);
@@ -353,20 +312,14 @@ int make_grid(const double origin[3], const double inv_cell[3],
         g->origin[i] = origin[i];
         g->inv_cell[i] = inv_cell[i];
         g->ncell[i] = ncell[i];
-        ncells *= ncell[i];
-    }
-    if (ncells > PAIRS_MAX_CELLS) {
-        NBK_SET_ERR("%s: %lld cells exceed the %lld-cell LDS histogram",
-                    who, (long long)ncells, (long long)PAIRS_MAX_CELLS);
-        return NBK_ERR_ARG;
+        *ncells *= ncell[i];
+        if (*ncells > NBK_SORT_LDS_INTS) {
+            NBK_SET_ERR("%s: more than %lld cells, the LDS histogram",
+                        who, (long long)NBK_SORT_LDS_INTS);
+            return NBK_ERR_ARG;
+        }
     }
     return NBK_OK;
-}
-
-void raise_lds(const void* fn, size_t bytes) {
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(fn,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 size_t count_lds_bytes(int mode, int nb0, int ns, int ncopy) {
@@ -384,25 +337,14 @@ extern "C" int nbk_pairs_cell_count_f64(const double* pos_aos, int64_t n,
                                         const int ncell[3], int* mat,
                                         void* stream)
 {
-    PairsGrid g;
-    const int rc = make_grid(origin, inv_cell, ncell, &g,
-                             "nbk_pairs_cell_count_f64");
+    const char* who = "nbk_pairs_cell_count_f64";
+    PairsCellKey g;
+    int64_t ncells;
+    const int rc = make_grid(who, origin, inv_cell, ncell, &g, &ncells);
     if (rc != NBK_OK) return rc;
-    if (n < 0 || n >= ((int64_t)1 << 31) || chunk < 1) {
-        NBK_SET_ERR("nbk_pairs_cell_count_f64: n=%lld chunk=%d",
-                    (long long)n, chunk);
-        return NBK_ERR_ARG;
-    }
-    if (n == 0) return NBK_OK;
-    const int ncells = ncell[0] * ncell[1] * ncell[2];
-    const int64_t nblocks = (n + chunk - 1) / chunk;
-    const size_t lds = (size_t)ncells * sizeof(int);
-    raise_lds(reinterpret_cast<const void*>(&kpairs_cell_count), lds);
-    hipLaunchKernelGGL(kpairs_cell_count, dim3((uint32_t)nblocks),
-                       dim3(1024), lds, (hipStream_t)stream, pos_aos, n,
-                       chunk, g, ncells, mat);
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    return countsort_count<PairsCellKey, false>(who, pos_aos, n, chunk, g,
+                                                ncells, mat, nullptr,
+                                                stream);
 }
 
 extern "C" int nbk_pairs_cell_scatter_f64(const double* pos_aos,
@@ -414,26 +356,13 @@ extern "C" int nbk_pairs_cell_scatter_f64(const double* pos_aos,
                                           double* pos_out, double* w_out,
                                           void* stream)
 {
-    PairsGrid g;
-    const int rc = make_grid(origin, inv_cell, ncell, &g,
-                             "nbk_pairs_cell_scatter_f64");
+    const char* who = "nbk_pairs_cell_scatter_f64";
+    PairsCellKey g;
+    int64_t ncells;
+    const int rc = make_grid(who, origin, inv_cell, ncell, &g, &ncells);
     if (rc != NBK_OK) return rc;
-    if (n < 0 || n >= ((int64_t)1 << 31) || chunk < 1) {
-        NBK_SET_ERR("nbk_pairs_cell_scatter_f64: n=%lld chunk=%d",
-                    (long long)n, chunk);
-        return NBK_ERR_ARG;
-    }
-    if (n == 0) return NBK_OK;
-    const int ncells = ncell[0] * ncell[1] * ncell[2];
-    const int64_t nblocks = (n + chunk - 1) / chunk;
-    const size_t lds = (size_t)ncells * sizeof(int);
-    raise_lds(reinterpret_cast<const void*>(&kpairs_cell_scatter), lds);
-    hipLaunchKernelGGL(kpairs_cell_scatter, dim3((uint32_t)nblocks),
-                       dim3(1024), lds, (hipStream_t)stream, pos_aos,
-                       weight, n, chunk, g, ncells, bases, pos_out,
-                       pos_out + n, pos_out + 2 * n, w_out);
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    return countsort_scatter(who, pos_aos, weight, n, chunk, g, ncells,
+                             bases, n, pos_out, w_out, stream);
 }
 
 extern "C" int nbk_pairs_max_bins(void) { return NBK_PAIRS_MAX_BINS; }
@@ -478,7 +407,7 @@ extern "C" int nbk_pairs_count_f64(const double* pos1, const double* w1,
         }
         ncells *= ncell[i];
     }
-    if (ncells > PAIRS_MAX_CELLS) {
+    if (ncells > NBK_SORT_LDS_INTS) {
         NBK_SET_ERR("%s: too many cells (%lld)", who, (long long)ncells);
         return NBK_ERR_ARG;
     }

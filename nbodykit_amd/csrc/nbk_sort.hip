@@ -1,23 +1,27 @@
 // Particle locality sorts for the paint kernels.
 //
-// Two pipelines:
-// - nbk_xsort_count/scatter + nbk_bucket_fine (big meshes): a
-//   two-level ATOMIC-FREE counting sort.  The global atomic pipe runs
-//   at ~25 G op/s regardless of locality (csrc/count_probe.hip), so no
-//   stage may use global atomics: the coarse sort by
-//   (ix, iy-group) goes through per-chunk count MATRICES (host-scanned,
-//   no shared ticket counters) + LDS cursors, and the fine pass runs
-//   count + block scan + placement entirely in LDS, one block per
-//   coarse bucket.  Row-only fine mode serves the ownership-gather
-//   paint (which needs row grouping, not full cell order) and emits
-//   the row table it reads.
+// Two count-matrix sorts (the atomic-free scheme of nbk_countsort.h) and
+// one ticket sort:
+// - nbk_xsort_count/scatter + nbk_bucket_fine (big meshes, the two-level
+//   sort): the coarse key is (ix, iy-group); the fine pass then runs
+//   count + block scan + placement entirely in LDS, one block per coarse
+//   bucket.  Row-only fine mode serves the ownership-gather paint (which
+//   needs row grouping, not full cell order) and emits the row table it
+//   reads.
+// - nbk_psort_count/scatter (big meshes, CIC): the key is (x-plane pair,
+//   iy-group) with stencil-boundary particles duplicated into both
+//   groups, so the gather paint reads bucket ranges and no fine pass
+//   runs.
 // - nbk_bucket_count/scatter (small inputs): the single-level counting
-//   sort by full cell id with int32 countdown tickets, paired with the
-//   wave-merged scatter paint.
+//   sort by full cell id with int32 countdown tickets (global atomics),
+//   paired with the wave-merged scatter paint.
+// nbk_scan_matrix_i32, the scan between count and scatter, lives here
+// too and also serves the third key of the scheme, the pair counter's
+// cell id (nbk_pairs.hip).
 //
-// Both are non-stable within a bucket/cell (fine: deposits commute)
-// and emit SoA (x[n] y[n] z[n]) — the layout the paint kernels read.
-#include "nbk_common.h"
+// All are non-stable within a bucket/cell (fine: deposits commute) and
+// emit SoA (x[n] y[n] z[n]) — the layout the paint kernels read.
+#include "nbk_countsort.h"
 
 namespace {
 
@@ -94,89 +98,36 @@ __global__ void kbucket_scatter(const double* __restrict__ pos,
     }
 }
 
-// ---- chunked x-plane pre-sort (the coarse level) ----------------------
-// Deterministic counting sort by wrapped x-plane index, with NO global
-// atomics: pass A writes one histogram row per chunk to a [nchunks x n0]
-// matrix, the host scans it bucket-major, and pass C places each chunk's
-// particles from LDS cursors seeded by the scanned bases.  Running the
-// fine cell sort on this output makes its scattered counter/ticket
-// atomics hit 64-byte lines ~16x each (one x-plane's counters span
-// n1*n2*4 B) instead of thrashing the whole multi-GB array.
+// ---- coarse key of the two-level sort ---------------------------------
+// Running the fine cell sort on the coarse-sorted output keeps each
+// block's cells inside one LDS window instead of thrashing the whole
+// multi-GB array.
 
 // coarse key: ix * (n1 >> ys) + (iy >> ys) — ys chosen by the host so
 // that BOTH the coarse histogram (nbuckets ints) and the fine pass's
-// per-bucket cell window ((1 << ys) * n2 ints) fit in LDS
-__device__ __forceinline__ int64_t coarse_key(double x, double y,
-                                              double invH0, double invH1,
-                                              int64_t n0, int64_t n1,
-                                              int ys) {
-    const int64_t ix = wrap_idx((int64_t)floor(x * invH0), n0);
-    const int64_t iy = wrap_idx((int64_t)floor(y * invH1), n1);
-    return ix * (n1 >> ys) + (iy >> ys);
-}
+// per-bucket cell window ((1 << ys) * n2 ints) fit in LDS.  The scatter
+// emits SoA planes so the fine pass's counting loop can read the
+// 8 B/particle y plane instead of 24 B AoS rows — 16 GB less traffic at
+// C4 (fine reads y twice: count + scatter).
+struct XsortKey {
+    typedef int64_t index_t;
+    static constexpr bool two_keys = false;
+    int64_t n0, n1, n2;
+    double invH0, invH1, invH2;
+    int ys;
 
-__global__ void kxsort_count(const double* __restrict__ pos, int64_t n,
-                             int chunk, int64_t n0, int64_t n1, int64_t n2,
-                             double invH0, double invH1, double invH2,
-                             int ys, int64_t nbuck,
-                             int* __restrict__ mat,
-                             int* __restrict__ scrambled_flag)
-{
-    extern __shared__ int hist[];   // nbuck ints
-    for (int64_t b = threadIdx.x; b < nbuck; b += blockDim.x) hist[b] = 0;
-    __syncthreads();
-    const int64_t beg = (int64_t)blockIdx.x * chunk;
-    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
-    const int lane = threadIdx.x & 63;
-    int out_of_order = 0;
-    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const double x = pos[3 * i], y = pos[3 * i + 1],
-                     z = pos[3 * i + 2];
-        atomicAdd(&hist[coarse_key(x, y, invH0, invH1, n0, n1, ys)], 1);
-        if (scrambled_flag) {
-            const int64_t b = bucket_of(x, y, z, invH0, invH1, invH2,
-                                        n0, n1, n2, 0);
-            const int64_t b_up = __shfl_up((long long)b, 1, 64);
-            if (lane > 0 && b_up > b) out_of_order = 1;
-        }
+    __device__ __forceinline__ int64_t operator()(double x, double y,
+                                                  double) const {
+        const int64_t ix = wrap_idx((int64_t)floor(x * invH0), n0);
+        const int64_t iy = wrap_idx((int64_t)floor(y * invH1), n1);
+        return ix * (n1 >> ys) + (iy >> ys);
     }
-    if (out_of_order) atomicOr(scrambled_flag, 1);
-    __syncthreads();
-    for (int64_t b = threadIdx.x; b < nbuck; b += blockDim.x)
-        mat[(int64_t)blockIdx.x * nbuck + b] = hist[b];
-}
-
-// emits SoA planes (ox/oy/oz) so the fine pass's counting loop can read
-// the 8 B/particle y plane instead of 24 B AoS rows — 16 GB less
-// traffic at C4 (fine reads y twice: count + scatter)
-__global__ void kxsort_scatter(const double* __restrict__ pos,
-                               const double* __restrict__ mass, int64_t n,
-                               int chunk, int64_t n0, int64_t n1,
-                               double invH0, double invH1,
-                               int ys, int64_t nbuck,
-                               const int* __restrict__ bases,
-                               double* __restrict__ ox,
-                               double* __restrict__ oy,
-                               double* __restrict__ oz,
-                               double* __restrict__ om)
-{
-    extern __shared__ int cur[];    // nbuck running cursors
-    for (int64_t b = threadIdx.x; b < nbuck; b += blockDim.x)
-        cur[b] = bases[(int64_t)blockIdx.x * nbuck + b];
-    __syncthreads();
-    const int64_t beg = (int64_t)blockIdx.x * chunk;
-    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
-    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const double x = pos[3 * i], y = pos[3 * i + 1],
-                     z = pos[3 * i + 2];
-        const int64_t k = coarse_key(x, y, invH0, invH1, n0, n1, ys);
-        const int64_t t = (int64_t)atomicAdd(&cur[k], 1);
-        ox[t] = x;
-        oy[t] = y;
-        oz[t] = z;
-        if (mass) om[t] = mass[i];
+    // full cell id: the order the two-level sort produces
+    __device__ __forceinline__ int64_t order_key(double x, double y,
+                                                 double z) const {
+        return bucket_of(x, y, z, invH0, invH1, invH2, n0, n1, n2, 0);
     }
-}
+};
 
 // ---- count-matrix scan (replaces the torch transpose/cumsum glue) ----
 // mat is [nblocks x nbuck] chunk-major.  Produces bases[c][b] =
@@ -222,13 +173,12 @@ __global__ void kscan_fold(const int* __restrict__ partial,
     colsum[b] = s;
 }
 
-// single-block exclusive scan of colsum (nbuck <= 40960): writes the
-// exclusive base back into colsum and the inclusive edges into
-// bucket_bases[1..nbuck] (bucket_bases[0] = 0)
+// single-block exclusive scan of colsum (nbuck <= NBK_SORT_LDS_INTS):
+// writes the exclusive base back into colsum and the inclusive edges
+// into bucket_bases[1..nbuck] (bucket_bases[0] = 0)
 __global__ void kscan_exclusive(int* __restrict__ colsum, int64_t nbuck,
                                 int* __restrict__ bucket_bases)
 {
-    __shared__ int wsum[17];
     const int T = blockDim.x;
     const int t = threadIdx.x;
     const int S = (int)((nbuck + T - 1) / T);
@@ -237,26 +187,7 @@ __global__ void kscan_exclusive(int* __restrict__ colsum, int64_t nbuck,
         const int64_t idx = (int64_t)t * S + j;
         if (idx < nbuck) acc += colsum[idx];
     }
-    const int lane = t & 63;
-    const int wave = t >> 6;
-    int v = acc;
-    #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int w = 0; w < (T >> 6); w++) {
-            const int x = wsum[w];
-            wsum[w] = run;
-            run += x;
-        }
-    }
-    __syncthreads();
-    int run = wsum[wave] + (v - acc);
+    int run = nbk_block_exclusive_scan(acc);
     for (int j = 0; j < S; j++) {
         const int64_t idx = (int64_t)t * S + j;
         if (idx < nbuck) {
@@ -315,7 +246,6 @@ __global__ void kbucket_fine(const double* __restrict__ px,
                                  paint kernel */)
 {
     extern __shared__ int lds[];            // win ints (counts->cursors)
-    __shared__ int ssum[16];
     const int64_t win = ((int64_t)1 << ys) * n2;
     const int64_t ymask = ((int64_t)1 << ys) - 1;
     const int T = blockDim.x;
@@ -334,32 +264,11 @@ __global__ void kbucket_fine(const double* __restrict__ px,
     }
     __syncthreads();
 
-    // block-wide exclusive scan of lds[0..win), seeded with beg:
-    // stripes per thread, wave shfl scan of the stripe sums, serial
-    // scan of the wave totals
+    // block-wide exclusive scan of lds[0..win), seeded with beg
     const int S = (int)(win / T);           // win % T == 0 (host guard)
     int acc = 0;
     for (int j = 0; j < S; j++) acc += lds[t * S + j];
-    const int lane = t & 63;
-    const int wave = t >> 6;
-    int v = acc;
-    #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    if (lane == 63) ssum[wave] = v;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int w = 0; w < (T >> 6); w++) {
-            const int x = ssum[w];
-            ssum[w] = run;
-            run += x;
-        }
-    }
-    __syncthreads();
-    int run = (int)beg + ssum[wave] + (v - acc);
+    int run = (int)beg + nbk_block_exclusive_scan(acc);
     for (int j = 0; j < S; j++) {
         const int c = lds[t * S + j];
         lds[t * S + j] = run;
@@ -460,9 +369,9 @@ __global__ void kbucket_fine_rows(const double* __restrict__ px,
 }
 
 
-// ---- PAIR-BUCKET sort (the fine-pass eliminator) ---------------------
+// ---- PAIR-BUCKET key (the fine-pass eliminator) -----------------------
 // Key = (x-plane PAIR, y row-GROUP) with nbuck = (n0/2) * (n1 >> ys)
-// <= 40960 (i32 LDS histograms), and particles DUPLICATED into every
+// i32 LDS histogram entries, and particles DUPLICATED into every
 // y-group their deposit stencil touches (rows [iy+dlo, iy+dhi]; the
 // stencil spans <= 5 rows << the group size, so <= 2 copies).  The
 // ownership-gather paint then reads each (pair, group) bucket range
@@ -470,79 +379,26 @@ __global__ void kbucket_fine_rows(const double* __restrict__ px,
 // whole per-row fine pass (56 GB of moves at C4) disappears.  The cost
 // moves into the paint's source reads: a pair bucket holds ~3 planes
 // of particles, read by each of the pair's 2 tiles.
-__device__ __forceinline__ void pair_keys(double x, double y,
-                                          double invH0, double invH1,
-                                          int64_t n0, int64_t n1, int ys,
-                                          int dlo, int dhi,
-                                          int64_t* k1, int64_t* k2) {
-    const int64_t ix = wrap_idx((int64_t)floor(x * invH0), n0);
-    const int64_t iy = (int64_t)floor(y * invH1);
-    const int64_t ng = n1 >> ys;
-    const int64_t g1 = wrap_idx(iy + dlo, n1) >> ys;
-    const int64_t g2 = wrap_idx(iy + dhi, n1) >> ys;
-    const int64_t base = (ix >> 1) * ng;
-    *k1 = base + g1;
-    *k2 = (g2 == g1) ? -1 : base + g2;
-}
+struct PsortKey {
+    typedef int64_t index_t;
+    static constexpr bool two_keys = true;
+    int64_t n0, n1;
+    double invH0, invH1;
+    int ys, dlo, dhi;
 
-__global__ void kpsort_count(const double* __restrict__ pos, int64_t n,
-                             int chunk, int64_t n0, int64_t n1,
-                             double invH0, double invH1,
-                             int ys, int dlo, int dhi, int64_t nbuck,
-                             int* __restrict__ mat)
-{
-    extern __shared__ int hist[];   // nbuck ints
-    for (int64_t b = threadIdx.x; b < nbuck; b += blockDim.x) hist[b] = 0;
-    __syncthreads();
-    const int64_t beg = (int64_t)blockIdx.x * chunk;
-    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
-    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        int64_t k1, k2;
-        pair_keys(pos[3 * i], pos[3 * i + 1], invH0, invH1, n0, n1,
-                  ys, dlo, dhi, &k1, &k2);
-        atomicAdd(&hist[k1], 1);
-        if (k2 >= 0) atomicAdd(&hist[k2], 1);
+    __device__ __forceinline__ int64_t operator()(double x, double y,
+                                                  double,
+                                                  int64_t* k2) const {
+        const int64_t ix = wrap_idx((int64_t)floor(x * invH0), n0);
+        const int64_t iy = (int64_t)floor(y * invH1);
+        const int64_t ng = n1 >> ys;
+        const int64_t g1 = wrap_idx(iy + dlo, n1) >> ys;
+        const int64_t g2 = wrap_idx(iy + dhi, n1) >> ys;
+        const int64_t base = (ix >> 1) * ng;
+        *k2 = (g2 == g1) ? -1 : base + g2;
+        return base + g1;
     }
-    __syncthreads();
-    for (int64_t b = threadIdx.x; b < nbuck; b += blockDim.x)
-        mat[(int64_t)blockIdx.x * nbuck + b] = hist[b];
-}
-
-__global__ void kpsort_scatter(const double* __restrict__ pos,
-                               const double* __restrict__ mass, int64_t n,
-                               int chunk, int64_t n0, int64_t n1,
-                               double invH0, double invH1,
-                               int ys, int dlo, int dhi, int64_t nbuck,
-                               const int* __restrict__ bases,
-                               int64_t n_out,
-                               double* __restrict__ ox,
-                               double* __restrict__ oy,
-                               double* __restrict__ oz,
-                               double* __restrict__ om)
-{
-    extern __shared__ int cur[];    // nbuck running cursors
-    for (int64_t b = threadIdx.x; b < nbuck; b += blockDim.x)
-        cur[b] = bases[(int64_t)blockIdx.x * nbuck + b];
-    __syncthreads();
-    const int64_t beg = (int64_t)blockIdx.x * chunk;
-    const int64_t end = (beg + chunk < n) ? beg + chunk : n;
-    for (int64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const double x = pos[3 * i], y = pos[3 * i + 1],
-                     z = pos[3 * i + 2];
-        int64_t k1, k2;
-        pair_keys(x, y, invH0, invH1, n0, n1, ys, dlo, dhi, &k1, &k2);
-        const double m = mass ? mass[i] : 0.0;
-        int64_t t = (int64_t)atomicAdd(&cur[k1], 1);
-        ox[t] = x; oy[t] = y; oz[t] = z;
-        if (mass) om[t] = m;
-        if (k2 >= 0) {
-            t = (int64_t)atomicAdd(&cur[k2], 1);
-            ox[t] = x; oy[t] = y; oz[t] = z;
-            if (mass) om[t] = m;
-        }
-    }
-    (void)n_out;
-}
+};
 
 int sgrid(int64_t n) {
     int64_t g = (n + 255) / 256;
@@ -600,14 +456,38 @@ extern "C" int nbk_bucket_scatter_f64(const double* pos_aos,
 }
 
 namespace {
-// LDS ceiling for the sort kernels, in int entries (160 KiB on gfx950)
-const int64_t NBK_SORT_LDS_INTS = 40960;
 
-void raise_lds(const void* fn, size_t bytes) {
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(fn,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// geometry checks + key of nbk_xsort_*; `who` names the entry point
+int xsort_key(const char* who, const int64_t nmesh[3], const double box[3],
+              int ys, XsortKey* key, int64_t* nbuck)
+{
+    if (ys < 0 || ys > 30 || (nmesh[1] % ((int64_t)1 << ys))) {
+        NBK_SET_ERR("%s: bad ys=%d for mesh", who, ys);
+        return NBK_ERR_ARG;
+    }
+    *key = {nmesh[0], nmesh[1], nmesh[2], nmesh[0] / box[0],
+            nmesh[1] / box[1], nmesh[2] / box[2], ys};
+    *nbuck = nmesh[0] * (nmesh[1] >> ys);
+    return NBK_OK;
 }
+
+// geometry checks + key of nbk_psort_*
+int psort_key(const char* who, const int64_t nmesh[3], const double box[3],
+              int ys, int dlo, int dhi, PsortKey* key, int64_t* nbuck)
+{
+    if (ys < 0 || ys > 30 || (nmesh[0] & 1)
+        || (nmesh[1] % ((int64_t)1 << ys))
+        || (dhi - dlo) >= ((int64_t)1 << ys)) {
+        NBK_SET_ERR("%s: bad geometry ys=%d dlo=%d dhi=%d", who, ys, dlo,
+                    dhi);
+        return NBK_ERR_ARG;
+    }
+    *key = {nmesh[0], nmesh[1], nmesh[0] / box[0], nmesh[1] / box[1], ys,
+            dlo, dhi};
+    *nbuck = (nmesh[0] >> 1) * (nmesh[1] >> ys);
+    return NBK_OK;
+}
+
 }  // namespace
 
 extern "C" int nbk_xsort_count_f64(const double* pos_aos, int64_t n,
@@ -615,22 +495,14 @@ extern "C" int nbk_xsort_count_f64(const double* pos_aos, int64_t n,
                                    const double box[3], int ys, int* mat,
                                    int* scrambled_flag, void* stream)
 {
-    if (n == 0) return NBK_OK;
-    const int64_t nbuck = nmesh[0] * (nmesh[1] >> ys);
-    if (nbuck > NBK_SORT_LDS_INTS || (nmesh[1] % ((int64_t)1 << ys))) {
-        NBK_SET_ERR("nbk_xsort_count_f64: bad ys=%d for mesh", ys);
-        return NBK_ERR_ARG;
-    }
-    const int64_t nblocks = (n + chunk - 1) / chunk;
-    const size_t lds = (size_t)nbuck * sizeof(int);
-    raise_lds(reinterpret_cast<const void*>(&kxsort_count), lds);
-    hipLaunchKernelGGL(kxsort_count, dim3((uint32_t)nblocks), dim3(1024),
-                       lds, (hipStream_t)stream, pos_aos, n, chunk,
-                       nmesh[0], nmesh[1], nmesh[2],
-                       nmesh[0] / box[0], nmesh[1] / box[1],
-                       nmesh[2] / box[2], ys, nbuck, mat, scrambled_flag);
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    const char* who = "nbk_xsort_count_f64";
+    XsortKey key;
+    int64_t nbuck;
+    const int rc = xsort_key(who, nmesh, box, ys, &key, &nbuck);
+    if (rc != NBK_OK) return rc;
+    return countsort_count<XsortKey, true>(who, pos_aos, n, chunk, key,
+                                           nbuck, mat, scrambled_flag,
+                                           stream);
 }
 
 extern "C" int nbk_xsort_scatter_f64(const double* pos_aos,
@@ -641,23 +513,13 @@ extern "C" int nbk_xsort_scatter_f64(const double* pos_aos,
                                      double* pos_out, double* mass_out,
                                      void* stream)
 {
-    if (n == 0) return NBK_OK;
-    const int64_t nbuck = nmesh[0] * (nmesh[1] >> ys);
-    if (nbuck > NBK_SORT_LDS_INTS || (nmesh[1] % ((int64_t)1 << ys))) {
-        NBK_SET_ERR("nbk_xsort_scatter_f64: bad ys=%d for mesh", ys);
-        return NBK_ERR_ARG;
-    }
-    const int64_t nblocks = (n + chunk - 1) / chunk;
-    const size_t lds = (size_t)nbuck * sizeof(int);
-    raise_lds(reinterpret_cast<const void*>(&kxsort_scatter), lds);
-    hipLaunchKernelGGL(kxsort_scatter, dim3((uint32_t)nblocks),
-                       dim3(1024), lds, (hipStream_t)stream, pos_aos,
-                       mass, n, chunk, nmesh[0], nmesh[1],
-                       nmesh[0] / box[0], nmesh[1] / box[1], ys, nbuck,
-                       bases, pos_out, pos_out + n, pos_out + 2 * n,
-                       mass_out);
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    const char* who = "nbk_xsort_scatter_f64";
+    XsortKey key;
+    int64_t nbuck;
+    const int rc = xsort_key(who, nmesh, box, ys, &key, &nbuck);
+    if (rc != NBK_OK) return rc;
+    return countsort_scatter(who, pos_aos, mass, n, chunk, key, nbuck,
+                             bases, n, pos_out, mass_out, stream);
 }
 
 /* colsum_tmp must hold (NBK_SCAN_SEG + 1) * nbuck ints: segment
@@ -738,24 +600,13 @@ extern "C" int nbk_psort_count_f64(const double* pos_aos, int64_t n,
                                    int dlo, int dhi, int* mat,
                                    void* stream)
 {
-    if (n == 0) return NBK_OK;
-    const int64_t nbuck = (nmesh[0] >> 1) * (nmesh[1] >> ys);
-    if (nbuck > NBK_SORT_LDS_INTS || (nmesh[0] & 1)
-        || (nmesh[1] % ((int64_t)1 << ys))
-        || (dhi - dlo) >= ((int64_t)1 << ys)) {
-        NBK_SET_ERR("nbk_psort_count_f64: bad geometry ys=%d", ys);
-        return NBK_ERR_ARG;
-    }
-    const int64_t nblocks = (n + chunk - 1) / chunk;
-    const size_t lds = (size_t)nbuck * sizeof(int);
-    raise_lds(reinterpret_cast<const void*>(&kpsort_count), lds);
-    hipLaunchKernelGGL(kpsort_count, dim3((uint32_t)nblocks), dim3(1024),
-                       lds, (hipStream_t)stream, pos_aos, n, chunk,
-                       nmesh[0], nmesh[1],
-                       nmesh[0] / box[0], nmesh[1] / box[1],
-                       ys, dlo, dhi, nbuck, mat);
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    const char* who = "nbk_psort_count_f64";
+    PsortKey key;
+    int64_t nbuck;
+    const int rc = psort_key(who, nmesh, box, ys, dlo, dhi, &key, &nbuck);
+    if (rc != NBK_OK) return rc;
+    return countsort_count<PsortKey, false>(who, pos_aos, n, chunk, key,
+                                            nbuck, mat, nullptr, stream);
 }
 
 extern "C" int nbk_psort_scatter_f64(const double* pos_aos,
@@ -767,22 +618,11 @@ extern "C" int nbk_psort_scatter_f64(const double* pos_aos,
                                      double* pos_out, double* mass_out,
                                      void* stream)
 {
-    if (n == 0) return NBK_OK;
-    const int64_t nbuck = (nmesh[0] >> 1) * (nmesh[1] >> ys);
-    if (nbuck > NBK_SORT_LDS_INTS) {
-        NBK_SET_ERR("nbk_psort_scatter_f64: bad ys=%d", ys);
-        return NBK_ERR_ARG;
-    }
-    const int64_t nblocks = (n + chunk - 1) / chunk;
-    const size_t lds = (size_t)nbuck * sizeof(int);
-    raise_lds(reinterpret_cast<const void*>(&kpsort_scatter), lds);
-    hipLaunchKernelGGL(kpsort_scatter, dim3((uint32_t)nblocks),
-                       dim3(1024), lds, (hipStream_t)stream, pos_aos,
-                       mass, n, chunk, nmesh[0], nmesh[1],
-                       nmesh[0] / box[0], nmesh[1] / box[1],
-                       ys, dlo, dhi, nbuck, bases, n_out,
-                       pos_out, pos_out + n_out, pos_out + 2 * n_out,
-                       mass_out);
-    NBK_CHECK_HIP(hipGetLastError());
-    return NBK_OK;
+    const char* who = "nbk_psort_scatter_f64";
+    PsortKey key;
+    int64_t nbuck;
+    const int rc = psort_key(who, nmesh, box, ys, dlo, dhi, &key, &nbuck);
+    if (rc != NBK_OK) return rc;
+    return countsort_scatter(who, pos_aos, mass, n, chunk, key, nbuck,
+                             bases, n_out, pos_out, mass_out, stream);
 }

@@ -256,3 +256,33 @@ def dptr(tensor):
 def cur_stream():
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ---- the count-matrix sorts (csrc/nbk_countsort.h) ------------------------
+
+# LDS ceiling of a sort histogram, cursor array or fine window, in int32
+# entries (NBK_SORT_LDS_INTS: 160 KiB)
+SORT_LDS_INTS = 40960
+
+# column segments of nbk_scan_matrix_i32 (NBK_SCAN_SEG in
+# csrc/nbk_sort.hip); its scratch holds one partial row per segment plus
+# the column sums
+_SCAN_SEG = 8
+
+
+def scan_count_matrix(lib, mat, nblocks, nbuck, stream, bucket_bases=None):
+    """Device scan of the [nblocks x nbuck] int32 count matrix a sort's
+    count step filled: returns (bases, bucket_bases), the per-chunk
+    cursor seeds its scatter step reads and the nbuck + 1 bucket edges
+    (written into ``bucket_bases`` when the caller passes one)."""
+    import torch
+    colsum = torch.empty((_SCAN_SEG + 1) * nbuck, dtype=torch.int32,
+                         device='cuda')
+    bases = torch.empty(nblocks * nbuck, dtype=torch.int32, device='cuda')
+    if bucket_bases is None:
+        bucket_bases = torch.empty(nbuck + 1, dtype=torch.int32,
+                                   device='cuda')
+    check(lib.nbk_scan_matrix_i32(
+        dptr(mat), nblocks, nbuck, dptr(colsum), dptr(bases),
+        dptr(bucket_bases), stream), 'nbk_scan_matrix_i32')
+    return bases, bucket_bases

@@ -79,11 +79,11 @@ def _sort_chunk(n, nbuck):
 def _two_level_ys(pm):
     """The y-group shift of the two-level locality sort, or None when no
     LDS budget fits this mesh (coarse histogram n0*(n1>>ys) ints and fine
-    window (1<<ys)*n2 ints both <= 40960).  pm-only, so every rank of a
+    window (1<<ys)*n2 ints both <= hiplib.SORT_LDS_INTS).  pm-only, so every rank of a
     communicator computes the same answer — the fused to_complex_field
     path gates on it collectively."""
     n0, n1, n2 = (int(x) for x in pm.Nmesh)
-    LDSW = 40960
+    LDSW = hiplib.SORT_LDS_INTS
     for ys in range(0, max(1, n1.bit_length())):
         if (1 << ys) > n1 or n1 % (1 << ys):
             break
@@ -117,7 +117,8 @@ _PAIR_GHOST = {
 def _pair_gs(nmesh):
     """The y-group shift of the PAIR-BUCKET duplicating sort, or None
     when the geometry does not admit it (tile = 1 plane x 1<<gs rows x
-    (n2+4) doubles in LDS; (n0/2)*(n1>>gs) buckets <= 40960).
+    (n2+4) doubles in LDS; (n0/2)*(n1>>gs) buckets within
+    hiplib.SORT_LDS_INTS).
     ``nmesh`` is any 3-sequence (pm.Nmesh or a plain triple)."""
     n0, n1, n2 = (int(x) for x in nmesh)
     if n0 % 2:
@@ -129,7 +130,7 @@ def _pair_gs(nmesh):
             break
         if rg * (n2 + 4) * 8 > 160 * 1024:
             break
-        if (n0 >> 1) * (n1 >> gs) <= 40960:
+        if (n0 >> 1) * (n1 >> gs) <= hiplib.SORT_LDS_INTS:
             best = gs
     return best
 
@@ -225,7 +226,8 @@ def _prepare_particles(pos_t, mass_t, pm, force_rowtab=False,
     # matrix + host scan + LDS cursors, then a fused per-bucket fine
     # kernel (LDS count + block scan + placement) emitting the exact
     # cell order.  ys balances the two LDS budgets: coarse histogram
-    # n0*(n1>>ys) ints vs fine window (1<<ys)*n2 ints, both <= 40960.
+    # n0*(n1>>ys) ints vs fine window (1<<ys)*n2 ints, both within
+    # hiplib.SORT_LDS_INTS.
     big = (force_rowtab
            or (n >= _global_options['sort_two_level_min_n']
                and ncells > _global_options['sort_two_level_min_cells']))
@@ -257,16 +259,8 @@ def _prepare_particles(pos_t, mass_t, pm, force_rowtab=False,
         hiplib.check(lib.nbk_psort_count_f64(
             hiplib.dptr(pos_in), n, CH, nmesh, box, gs, dlo, dhi,
             hiplib.dptr(mat), stream), 'nbk_psort_count_f64')
-        colsum = torch.empty(9 * nbuck, dtype=torch.int32,
-                             device='cuda')   # 8 segment partials + sums
-        bases = torch.empty(nblocks * nbuck, dtype=torch.int32,
-                            device='cuda')
-        bucket_bases = torch.empty(nbuck + 1, dtype=torch.int32,
-                                   device='cuda')
-        hiplib.check(lib.nbk_scan_matrix_i32(
-            hiplib.dptr(mat), nblocks, nbuck, hiplib.dptr(colsum),
-            hiplib.dptr(bases), hiplib.dptr(bucket_bases), stream),
-            'nbk_scan_matrix_i32')
+        bases, bucket_bases = hiplib.scan_count_matrix(
+            lib, mat, nblocks, nbuck, stream)
         n_out = int(bucket_bases[-1].item())
         out = torch.empty(3 * n_out, dtype=torch.float64, device='cuda')
         out_m = None
@@ -299,16 +293,8 @@ def _prepare_particles(pos_t, mass_t, pm, force_rowtab=False,
             return pos_t.t().contiguous(), mass_t, True, None
         # one fused device scan of the count matrix (replaces a ~4 GB
         # torch transpose/cumsum/sub chain with ~1.5 coalesced passes)
-        colsum = torch.empty(9 * nbuck, dtype=torch.int32,
-                             device='cuda')   # 8 segment partials + sums
-        bases = torch.empty(nblocks * nbuck, dtype=torch.int32,
-                            device='cuda')
-        bucket_bases = torch.empty(nbuck + 1, dtype=torch.int32,
-                                   device='cuda')
-        hiplib.check(lib.nbk_scan_matrix_i32(
-            hiplib.dptr(mat), nblocks, nbuck, hiplib.dptr(colsum),
-            hiplib.dptr(bases), hiplib.dptr(bucket_bases), stream),
-            'nbk_scan_matrix_i32')
+        bases, bucket_bases = hiplib.scan_count_matrix(
+            lib, mat, nblocks, nbuck, stream)
         coarse = torch.empty(3 * n, dtype=torch.float64, device='cuda')
         mass_c = None
         if mass_t is not None:

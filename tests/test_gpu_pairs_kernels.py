@@ -220,6 +220,66 @@ def test_cell_sort_rejects_bad_arguments(lib):
     assert (host(mat) == 0).all()
 
 
+def test_weighted_cell_sort_beside_unweighted_mesh_sorts(lib):
+    """One scatter template serves all three keys, its mass pointer
+    nullable: in one process the cell sort moves its weights while the
+    two mesh sorts run with mass = NULL and leave `mass_out` alone.
+    Mesh and grid [8, 8, 8] over HBOX, 3 chunks."""
+    import sort_reference as sref
+    pos, w = ref.catalogue('H1')
+    n = len(pos)
+    nmesh = [8, 8, 8]
+    chunk = n // 3 + 1
+    assert -(-n // chunk) == 3
+    grid = ref.uniform_grid(ref.HBOX, nmesh) + (nmesh,)
+
+    def check_cell_sort():
+        check_sorted(run_cell_sort(lib, pos, w, *grid, chunk), pos, w)
+
+    def run_mesh_sort(count, scatter, keys, nbuck, extra):
+        """count -> scan -> scatter with mass = NULL; returns the number
+        of placed rows"""
+        nm, bx = hiplib.i64_arr(nmesh), hiplib.f64_arr(ref.HBOX)
+        pos_t = dev(pos)
+        mat = filled(3 * nbuck, -1, torch.int32)
+        tail = (None,) if count is lib.nbk_xsort_count_f64 else ()
+        hiplib.check(count(hiplib.dptr(pos_t), n, chunk, nm, bx, *extra,
+                           hiplib.dptr(mat), *tail, None), 'count')
+        want_mat = sref.chunk_histograms(keys, nbuck, chunk)
+        want_bases, want_bb = sref.scan_matrix(want_mat)
+        assert_array_equal(host(mat).reshape(3, nbuck), want_mat)
+        bases, _ = hiplib.scan_count_matrix(lib, mat, 3, nbuck, None)
+        assert_array_equal(host(bases).reshape(3, nbuck), want_bases)
+        n_out = int(want_bb[-1])
+        out, out_m = nan_f64(3 * n_out), nan_f64(n_out)
+        tail = (n_out,) if scatter is lib.nbk_psort_scatter_f64 else ()
+        hiplib.check(scatter(hiplib.dptr(pos_t), None, n, chunk, nm, bx,
+                             *extra, hiplib.dptr(bases), *tail,
+                             hiplib.dptr(out), hiplib.dptr(out_m), None),
+                     'scatter')
+        assert numpy.isnan(host(out_m)).all()       # NULL mass: untouched
+        dup = numpy.concatenate([k[k >= 0] for k in keys])
+        rows = numpy.concatenate([pos[k >= 0] for k in keys])
+        got_key = numpy.repeat(numpy.arange(nbuck), numpy.diff(want_bb))
+        assert_array_equal(
+            ref.canonical_rows(host(out).reshape(3, n_out).T, None, got_key),
+            ref.canonical_rows(rows, None, dup))
+        return n_out
+
+    check_cell_sort()
+    ys = 1
+    assert run_mesh_sort(
+        lib.nbk_xsort_count_f64, lib.nbk_xsort_scatter_f64,
+        (sref.coarse_keys(pos, nmesh, ref.HBOX, ys),), 8 * (8 >> ys),
+        (ys,)) == n
+    gs, dlo, dhi = 2, 0, 1
+    assert run_mesh_sort(
+        lib.nbk_psort_count_f64, lib.nbk_psort_scatter_f64,
+        sref.pair_keys(pos, nmesh, ref.HBOX, gs, dlo, dhi),
+        (8 >> 1) * (8 >> gs), (gs, dlo, dhi)) > n
+    check_cell_sort()
+
+
 # ---- the count kernel ---------------------------------------------------
 
 _sorted = {}

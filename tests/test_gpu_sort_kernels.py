@@ -470,6 +470,66 @@ def test_pair_sort_rejects_bad_geometry(lib):
     assert count([32, 48, 32], 5, 0, 1) == NBK_ERR_ARG    # n1 % group
 
 
+def test_count_matrix_steps_reject_bad_arguments(lib):
+    """chunk < 1, n >= 2^31 and, for the pair scatter, the geometries
+    its count step rejects: NBK_ERR_ARG, nothing launched.  Every
+    particle sits in cell (0, 0, .) and `bases` is all zero, so a scatter
+    step that did run would stay inside the 2000-row outputs."""
+    n = 1000
+    pos = numpy.full((n, 3), 0.1)
+    pos[:, 2] = numpy.linspace(0., BOX[2], n, endpoint=False)
+    pos_t = dev(pos)
+    mat = filled(40960, -7, torch.int32)
+    bases = filled(40960, 0, torch.int32)
+    out, out_m = nan_f64(3 * 2 * n), nan_f64(2 * n)
+    bx = hiplib.f64_arr(BOX)
+    n32 = hiplib.i64_arr(MESHES['n32'])
+    ys = _two_level_ys(SimpleNamespace(Nmesh=MESHES['n32']))
+
+    def xcount(n, chunk):
+        return lib.nbk_xsort_count_f64(
+            hiplib.dptr(pos_t), n, chunk, n32, bx, ys, hiplib.dptr(mat),
+            None, None)
+
+    def xscatter(n, chunk):
+        return lib.nbk_xsort_scatter_f64(
+            hiplib.dptr(pos_t), None, n, chunk, n32, bx, ys,
+            hiplib.dptr(bases), hiplib.dptr(out), None, None)
+
+    def pcount(n, chunk):
+        return lib.nbk_psort_count_f64(
+            hiplib.dptr(pos_t), n, chunk, n32, bx, PAIR_TEST_GS, 0, 1,
+            hiplib.dptr(mat), None)
+
+    def pscatter(n, chunk, nmesh=MESHES['n32'], gs=PAIR_TEST_GS, dlo=0,
+                 dhi=1):
+        return lib.nbk_psort_scatter_f64(
+            hiplib.dptr(pos_t), None, n, chunk, hiplib.i64_arr(nmesh), bx,
+            gs, dlo, dhi, hiplib.dptr(bases), 2 * n, hiplib.dptr(out),
+            hiplib.dptr(out_m), None)
+
+    for fn, name in [(xcount, 'nbk_xsort_count_f64'),
+                     (xscatter, 'nbk_xsort_scatter_f64'),
+                     (pcount, 'nbk_psort_count_f64'),
+                     (pscatter, 'nbk_psort_scatter_f64')]:
+        for bad_n, bad_chunk in [(n, 0), (2 ** 31, 4096)]:
+            assert fn(bad_n, bad_chunk) == NBK_ERR_ARG, (name, bad_n)
+            assert name in lib.nbk_last_error_string().decode()
+
+    # the geometries of test_pair_sort_rejects_bad_geometry
+    for nmesh, gs, dlo, dhi in [([32, 32, 32], 1, -1, 2),
+                                ([32, 32, 32], 2, -1, 3),
+                                ([3, 32, 32], 3, 0, 1),
+                                ([32, 48, 32], 5, 0, 1)]:
+        assert pscatter(n, 4096, nmesh, gs, dlo, dhi) == NBK_ERR_ARG, \
+            (nmesh, gs, dlo, dhi)
+        assert 'nbk_psort_scatter_f64' in lib.nbk_last_error_string().decode()
+
+    # nothing was launched: the outputs are as they were
+    assert (host(mat) == -7).all()
+    assert numpy.isnan(host(out)).all() and numpy.isnan(host(out_m)).all()
+
+
 # ---- (f) nbk_paint_gather_f64 vs oracle.paint ---------------------------
 
 def run_gather(lib, s, nmesh, window, shift, x0=0, nx=None, accumulate=0,
