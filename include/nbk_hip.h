@@ -465,6 +465,33 @@ int nbk_pairs_count_f64(const double* pos1, const double* w1,
                         int64_t* npairs, double* wsum, double* xsum,
                         void* stream);
 
+/* The same count for a sky catalogue seen from the origin (the compute
+ * core of SurveyDataPairCount): the line of sight of a pair is its
+ * midpoint direction.  The grid is never periodic.  With d = p1 - p2,
+ * l = p1 + p2, s2 = (dx^2 + dy^2) + dz^2, l2 = (lx^2 + ly^2) + lz^2 and
+ * dl = (dx lx + dy ly) + dz lz:
+ *   mode 3: bins of (s, mu);   q = s2, mu = |dl| / sqrt(l2 * s2); the last
+ *           mu bin takes every mu >= edges1[nb1] (rounding can give
+ *           1 + 1 ulp); a NaN mu (l2 = 0 or s2 = 0) is dropped
+ *   mode 4: bins of (rp, pi);  pi = sqrt((dl * dl) / l2), q = s2 - pi^2;
+ *           pi >= edges1[nb1], l2 = 0 and q < edges0_sq[0] are dropped
+ *   mode 5: bins of the angle between unit vectors; q = s2 (the squared
+ *           chord, edges0_sq = (2 sin(theta / 2))^2), nb1 = 1, and xsum
+ *           sums 2 asin(min(1, sqrt(q) / 2)) * (180 / pi), in degrees
+ * Every other argument, the slices, `partials` and the outputs are those
+ * of nbk_pairs_count_f64, whose modes 0-2 this entry point rejects (and
+ * which rejects 3-5). */
+int nbk_pairs_count_sky_f64(const double* pos1, const double* w1,
+                            const int* start1, int64_t n1,
+                            const double* pos2, const double* w2,
+                            const int* start2, int64_t n2,
+                            int autocorr, const int ncell[3],
+                            int mode, const double* edges0_sq, int nb0,
+                            const double* edges1, int nb1, int j0, int j1,
+                            int nblocks, void* partials,
+                            int64_t* npairs, double* wsum, double* xsum,
+                            void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

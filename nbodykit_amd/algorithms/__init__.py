@@ -4,5 +4,5 @@ from .fftcorr import FFTCorr
 from .fftrecon import FFTRecon
 from .convpower import ConvolvedFFTPower, FKPCatalog, FKPWeightFromNbar
 from .zhist import RedshiftHistogram
-from .pair_counters import SimulationBoxPairCount
-from .paircount_tpcf import SimulationBox2PCF
+from .pair_counters import SimulationBoxPairCount, SurveyDataPairCount
+from .paircount_tpcf import SimulationBox2PCF, SurveyData2PCF

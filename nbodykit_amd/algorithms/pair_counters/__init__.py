@@ -1,1 +1,2 @@
 from .simbox import SimulationBoxPairCount
+from .mocksurvey import SurveyDataPairCount

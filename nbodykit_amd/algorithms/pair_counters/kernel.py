@@ -2,7 +2,9 @@
 Device driver of the pair counter: cell grid, cell sort and the count
 passes over ``nbk_pairs_*`` (csrc/nbk_pairs.hip).  Replaces the
 Corrfunc.theory.DD / DDsmu / DDrppi calls of the reference's
-pair_counters/corrfunc/theory.py.  Everything here runs on the GPU; the
+pair_counters/corrfunc/theory.py, and with ``sky=True`` the
+DDsmu_mocks / DDrppi_mocks / DDtheta_mocks calls of corrfunc/mocks.py
+(SurveyDataPairCount).  Everything here runs on the GPU; the
 only host transfers are the bounding box (non-periodic runs) and the
 finished histograms.
 """
@@ -11,6 +13,10 @@ import numpy
 from nbodykit_amd import hiplib, profiling
 
 MODE_IDS = {'1d': 0, '2d': 1, 'projected': 2}
+# the modes of nbk_pairs_count_sky_f64: the line of sight of a pair is
+# its midpoint direction from the origin ('1d' has no line of sight and
+# stays mode 0 on a non-periodic grid)
+SKY_MODE_IDS = {'2d': 3, 'projected': 4, 'angular': 5}
 
 # cells per axis: the largest cube that fits the LDS histogram of the
 # cell sort
@@ -19,8 +25,16 @@ assert MAX_CELLS_PER_AXIS ** 3 <= hiplib.SORT_LDS_INTS \
     < (MAX_CELLS_PER_AXIS + 1) ** 3
 
 
+def chord_edges_sq(theta_edges):
+    """Squared chords of the unit sphere at angular edges in degrees."""
+    theta_edges = numpy.asarray(theta_edges, dtype='f8')
+    return (2 * numpy.sin(0.5 * numpy.deg2rad(theta_edges))) ** 2
+
+
 def max_3d_separation(mode, edges, pimax):
     """The largest 3-D separation a counted pair can have."""
+    if mode == 'angular':
+        return float(numpy.sqrt(numpy.max(chord_edges_sq(edges))))
     rmax = float(numpy.max(edges))
     if mode == 'projected':
         rmax = float(numpy.sqrt(rmax ** 2 + float(pimax) ** 2))
@@ -150,7 +164,7 @@ def single_pass_capacity():
 
 
 def count_pairs(mode, pos1, w1, pos2, w2, edges, edges2, box, periodic,
-                pimax=None, info=None):
+                pimax=None, info=None, sky=False):
     """
     Pair counts of device catalogues (``pos2 is None``: auto-correlation).
 
@@ -159,9 +173,17 @@ def count_pairs(mode, pos1, w1, pos2, w2, edges, edges2, box, periodic,
     None in '1d'.  Returns host arrays (npairs u8, wsum f8, xsum f8) of
     shape (nb0,) or (nb0, nb1).  ``info``, if a dict, receives the grid
     and the cell-start tables.
+
+    ``sky``: positions seen from the origin, never periodic; '2d' and
+    'projected' use the midpoint line of sight of every pair, 'angular'
+    takes unit vectors and ``edges`` in degrees, and xsum sums degrees.
     """
     import torch
     lib = hiplib.require()
+    if sky:
+        periodic = False
+    elif mode == 'angular':
+        raise ValueError("mode 'angular' needs sky=True")
     auto = pos2 is None
     edges = numpy.asarray(edges, dtype='f8')
     nb0 = len(edges) - 1
@@ -195,7 +217,10 @@ def count_pairs(mode, pos1, w1, pos2, w2, edges, edges2, box, periodic,
     n2 = n1 if auto else int(pos2.shape[0])
 
     dev = torch.device('cuda')
-    e0sq = torch.as_tensor(edges * edges).to(dev)
+    if mode == 'angular':
+        e0sq = torch.as_tensor(chord_edges_sq(edges)).to(dev)
+    else:
+        e0sq = torch.as_tensor(edges * edges).to(dev)
     e1 = None
     if edges2 is not None:
         e1 = torch.as_tensor(numpy.asarray(edges2, dtype='f8')).to(dev)
@@ -219,14 +244,20 @@ def count_pairs(mode, pos1, w1, pos2, w2, edges, edges2, box, periodic,
             nblocks = ncu * (2 if nb <= 2048 else 1)
             partials = torch.empty(3 * nblocks * nb, dtype=torch.float64,
                                    device=dev)
-            hiplib.check(lib.nbk_pairs_count_f64(
-                hiplib.dptr(s1), hiplib.dptr(sw1), hiplib.dptr(start1), n1,
-                hiplib.dptr(s2), hiplib.dptr(sw2), hiplib.dptr(start2), n2,
-                1 if auto else 0, ncell_c, box_c, 1 if periodic else 0,
-                MODE_IDS[mode], hiplib.dptr(e0sq), nb0, hiplib.dptr(e1),
-                nb1, j0, j1, nblocks, hiplib.dptr(partials),
-                hiplib.dptr(npairs), hiplib.dptr(wsum), hiplib.dptr(xsum),
-                stream), 'nbk_pairs_count_f64')
+            cats = (hiplib.dptr(s1), hiplib.dptr(sw1), hiplib.dptr(start1),
+                    n1, hiplib.dptr(s2), hiplib.dptr(sw2),
+                    hiplib.dptr(start2), n2, 1 if auto else 0, ncell_c)
+            bins = (hiplib.dptr(e0sq), nb0, hiplib.dptr(e1), nb1, j0, j1,
+                    nblocks, hiplib.dptr(partials), hiplib.dptr(npairs),
+                    hiplib.dptr(wsum), hiplib.dptr(xsum), stream)
+            if sky and mode in SKY_MODE_IDS:
+                hiplib.check(lib.nbk_pairs_count_sky_f64(
+                    *cats, SKY_MODE_IDS[mode], *bins),
+                    'nbk_pairs_count_sky_f64')
+            else:
+                hiplib.check(lib.nbk_pairs_count_f64(
+                    *cats, box_c, 1 if periodic else 0, MODE_IDS[mode],
+                    *bins), 'nbk_pairs_count_f64')
             npasses += 1
 
     if info is not None:

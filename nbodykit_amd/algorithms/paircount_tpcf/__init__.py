@@ -1,2 +1,2 @@
-from .tpcf import SimulationBox2PCF
+from .tpcf import SimulationBox2PCF, SurveyData2PCF
 from .estimators import WedgeBinnedStatistic

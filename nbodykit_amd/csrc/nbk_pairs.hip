@@ -92,7 +92,7 @@ struct PairsArgs {
     int ncopy;          // histogram copies per block (waves share mod)
     int split;          // work items per first-catalogue cell
     const double* e0sq; // nb0 + 1 squared first-dimension edges
-    const double* e1;   // nb1 + 1 second-dimension edges (modes 1, 2)
+    const double* e1;   // nb1 + 1 second-dimension edges (modes 1-4)
                         // — only the slice [j0, j1] is staged in LDS
     unsigned long long* part_n;   // [gridDim.x * nb] partials
     double* part_w;
@@ -120,7 +120,14 @@ __device__ __forceinline__ bool neighbour_axis(int c, int d, int n,
     return true;
 }
 
-// MODE 0: 1d (r), 1: 2d (r, mu), 2: projected (rp, pi)
+// modes without a second dimension
+__host__ __device__ constexpr bool mode_is_1d(int mode) {
+    return mode == 0 || mode == 5;
+}
+
+// MODE 0: 1d (r), 1: 2d (r, mu), 2: projected (rp, pi) along the last
+// axis; 3: (s, mu), 4: (rp, pi) along the pair's midpoint direction,
+// 5: angle between unit vectors (sky modes, never periodic)
 template <int MODE>
 __global__ __launch_bounds__(PAIRS_THREADS)
 void kpairs_count(PairsArgs a)
@@ -134,13 +141,13 @@ void kpairs_count(PairsArgs a)
     double* e0sq = reinterpret_cast<double*>(tzw + PAIRS_TILE);
     double* e1 = e0sq + (a.nb0 + 1);
     unsigned long long* hn = reinterpret_cast<unsigned long long*>(
-        e1 + (MODE == 0 ? 0 : ns + 1));
+        e1 + (mode_is_1d(MODE) ? 0 : ns + 1));
     double* hw = reinterpret_cast<double*>(hn + (size_t)a.ncopy * nb);
     double* hx = hw + (size_t)a.ncopy * nb;
 
     const int tid = threadIdx.x;
     for (int k = tid; k <= a.nb0; k += blockDim.x) e0sq[k] = a.e0sq[k];
-    if (MODE != 0)
+    if (!mode_is_1d(MODE))
         for (int k = tid; k <= ns; k += blockDim.x) e1[k] = a.e1[a.j0 + k];
     for (int k = tid; k < a.ncopy * nb; k += blockDim.x) {
         hn[k] = 0ull;
@@ -151,10 +158,20 @@ void kpairs_count(PairsArgs a)
 
     const double q_lo = e0sq[0], q_hi = e0sq[a.nb0];
     // this pass's slice [v_lo, v_hi) of the second dimension; the last
-    // mu bin is closed at 1 (mu <= 1 always)
-    const double v_lo = (MODE == 0) ? 0.0 : e1[0];
-    const double v_hi = (MODE == 0) ? 0.0 : e1[ns];
-    const bool closed = (MODE == 1) && a.j1 == a.nb1;
+    // mu bin is closed above (mu <= 1 along an axis; a midpoint mu that
+    // rounding pushes past 1 belongs to it too)
+    const double v_lo = mode_is_1d(MODE) ? 0.0 : e1[0];
+    const double v_hi = mode_is_1d(MODE) ? 0.0 : e1[ns];
+    const bool closed = (MODE == 1 || MODE == 3) && a.j1 == a.nb1;
+    // mode 4 rejects on s^2 before it knows pi: rp^2 = fl(s^2 - pi^2)
+    // >= q_lo needs s^2 >= q_lo (pi^2 >= 0 and s^2 is a double), and
+    // rp^2 < q_hi with pi < pimax needs s^2 < q_hi + pimax^2 up to a
+    // few roundings, which the factor 1 + 2^-40 covers many times over
+    double s_hi = q_hi;
+    if (MODE == 4) {
+        const double pimax = a.e1[a.nb1];
+        s_hi = (q_hi + pimax * pimax) * (1.0 + 0x1p-40);
+    }
     const int copy = ((tid >> 6) % a.ncopy) * nb;
     const int ncy = a.ncell[1], ncz = a.ncell[2];
     const int ncells = a.ncell[0] * ncy * ncz;
@@ -217,22 +234,45 @@ void kpairs_count(PairsArgs a)
                             for (int t = 0; t < nt; t++) {
                                 const double2 pxy = txy[t];
                                 const double2 pzw = tzw[t];
-                                const double dx = (xi - pxy.x) - sx;
-                                const double dy = (yi - pxy.y) - sy;
-                                const double dz = (zi - pzw.x) - sz;
+                                const double dx = (MODE >= 3)
+                                    ? xi - pxy.x : (xi - pxy.x) - sx;
+                                const double dy = (MODE >= 3)
+                                    ? yi - pxy.y : (yi - pxy.y) - sy;
+                                const double dz = (MODE >= 3)
+                                    ? zi - pzw.x : (zi - pzw.x) - sz;
                                 const double rp2 = dx * dx + dy * dy;
-                                const double q = (MODE == 2)
-                                               ? rp2 : rp2 + dz * dz;
-                                if (!(q >= q_lo && q < q_hi)) continue;
+                                double q = (MODE == 2)
+                                         ? rp2 : rp2 + dz * dz;
+                                if (!(q >= q_lo && q < s_hi)) continue;
                                 if (a.autocorr && t0 + t == i) continue;
+                                double v = 0.0;
+                                if (MODE == 3 || MODE == 4) {
+                                    const double lx = xi + pxy.x;
+                                    const double ly = yi + pxy.y;
+                                    const double lz = zi + pzw.x;
+                                    const double l2 = (lx * lx + ly * ly)
+                                                    + lz * lz;
+                                    const double dl = (dx * lx + dy * ly)
+                                                    + dz * lz;
+                                    if (MODE == 3) {
+                                        v = fabs(dl) / sqrt(l2 * q);
+                                    } else {
+                                        // (NaN for l = 0: dropped here)
+                                        const double pi2 = (dl * dl) / l2;
+                                        v = sqrt(pi2);
+                                        q = q - pi2;
+                                        if (!(q >= q_lo && q < q_hi))
+                                            continue;
+                                    }
+                                }
                                 const double r = sqrt(q);
+                                if (MODE == 1) v = fabs(dz) / r;
+                                if (MODE == 2) v = fabs(dz);
                                 int j = 0;
-                                if (MODE != 0) {
-                                    const double v = (MODE == 1)
-                                        ? fabs(dz) / r : fabs(dz);
-                                    // (also false for the NaN mu = 0/0
-                                    // of a pair at r = 0: it has no
-                                    // mu bin, in any pass)
+                                if (!mode_is_1d(MODE)) {
+                                    // (also false for a NaN mu = 0/0: a
+                                    // pair at r = 0, or p2 = -p1 in mode
+                                    // 3, has no mu bin, in any pass)
                                     if (!(v >= v_lo)) continue;
                                     if (v < v_hi)
                                         j = bin_search(e1, ns, v);
@@ -241,11 +281,17 @@ void kpairs_count(PairsArgs a)
                                     else
                                         continue;
                                 }
+                                // the accumulated first variable: r, rp
+                                // or the angle of the chord in degrees
+                                const double x = (MODE == 5)
+                                    ? (2.0 * asin(fmin(1.0, 0.5 * r)))
+                                      * (180.0 / M_PI)
+                                    : r;
                                 const int k = bin_search(e0sq, a.nb0, q);
                                 const int h = copy + k * ns + j;
                                 atomicAdd(&hn[h], 1ull);
                                 atomicAdd(&hw[h], wi * pzw.y);
-                                atomicAdd(&hx[h], r);
+                                atomicAdd(&hx[h], x);
                             }
                         }
                     }
@@ -325,66 +371,40 @@ int make_grid(const char* who, const double origin[3],
 size_t count_lds_bytes(int mode, int nb0, int ns, int ncopy) {
     return (size_t)PAIRS_TILE * 2 * sizeof(double2)
          + (size_t)(nb0 + 1) * sizeof(double)
-         + (mode == 0 ? 0 : (size_t)(ns + 1) * sizeof(double))
+         + (mode_is_1d(mode) ? 0 : (size_t)(ns + 1) * sizeof(double))
          + (size_t)ncopy * nb0 * ns * 24;
 }
 
-}  // namespace
-
-extern "C" int nbk_pairs_cell_count_f64(const double* pos_aos, int64_t n,
-                                        int chunk, const double origin[3],
-                                        const double inv_cell[3],
-                                        const int ncell[3], int* mat,
-                                        void* stream)
-{
-    const char* who = "nbk_pairs_cell_count_f64";
-    PairsCellKey g;
-    int64_t ncells;
-    const int rc = make_grid(who, origin, inv_cell, ncell, &g, &ncells);
-    if (rc != NBK_OK) return rc;
-    return countsort_count<PairsCellKey, false>(who, pos_aos, n, chunk, g,
-                                                ncells, mat, nullptr,
-                                                stream);
+template <int MODE>
+void launch_count(const PairsArgs& a, int nblocks, size_t lds,
+                  hipStream_t s) {
+    raise_lds(reinterpret_cast<const void*>(&kpairs_count<MODE>), lds);
+    hipLaunchKernelGGL(kpairs_count<MODE>, dim3((uint32_t)nblocks),
+                       dim3(PAIRS_THREADS), lds, s, a);
 }
 
-extern "C" int nbk_pairs_cell_scatter_f64(const double* pos_aos,
-                                          const double* weight, int64_t n,
-                                          int chunk, const double origin[3],
-                                          const double inv_cell[3],
-                                          const int ncell[3],
-                                          const int* bases,
-                                          double* pos_out, double* w_out,
-                                          void* stream)
+// validation, LDS sizing, histogram copies, work split, count and reduce
+// of both count entry points; `who` accepts modes [mode_lo, mode_hi]
+int count_pairs(const char* who, int mode_lo, int mode_hi,
+                const double* pos1, const double* w1, const int* start1,
+                int64_t n1, const double* pos2, const double* w2,
+                const int* start2, int64_t n2, int autocorr,
+                const int ncell[3], const double box[3], int periodic,
+                int mode, const double* edges0_sq, int nb0,
+                const double* edges1, int nb1, int j0, int j1, int nblocks,
+                void* partials, int64_t* npairs, double* wsum, double* xsum,
+                void* stream)
 {
-    const char* who = "nbk_pairs_cell_scatter_f64";
-    PairsCellKey g;
-    int64_t ncells;
-    const int rc = make_grid(who, origin, inv_cell, ncell, &g, &ncells);
-    if (rc != NBK_OK) return rc;
-    return countsort_scatter(who, pos_aos, weight, n, chunk, g, ncells,
-                             bases, n, pos_out, w_out, stream);
-}
-
-extern "C" int nbk_pairs_max_bins(void) { return NBK_PAIRS_MAX_BINS; }
-
-extern "C" int nbk_pairs_count_f64(const double* pos1, const double* w1,
-                                   const int* start1, int64_t n1,
-                                   const double* pos2, const double* w2,
-                                   const int* start2, int64_t n2,
-                                   int autocorr, const int ncell[3],
-                                   const double box[3], int periodic,
-                                   int mode, const double* edges0_sq,
-                                   int nb0, const double* edges1, int nb1,
-                                   int j0, int j1, int nblocks,
-                                   void* partials, int64_t* npairs,
-                                   double* wsum, double* xsum,
-                                   void* stream)
-{
-    const char* who = "nbk_pairs_count_f64";
-    if (mode < 0 || mode > 2 || nb0 < 1 || nb1 < 1
-        || (mode == 0 && nb1 != 1) || j0 < 0 || j1 > nb1 || j0 >= j1) {
+    if (mode < mode_lo || mode > mode_hi || nb0 < 1 || nb1 < 1
+        || (mode_is_1d(mode) && nb1 != 1) || j0 < 0 || j1 > nb1
+        || j0 >= j1) {
         NBK_SET_ERR("%s: bad mode/bins (mode=%d nb0=%d nb1=%d slice "
                     "[%d, %d))", who, mode, nb0, nb1, j0, j1);
+        return NBK_ERR_ARG;
+    }
+    if (edges0_sq == nullptr
+        || (!mode_is_1d(mode) && edges1 == nullptr)) {
+        NBK_SET_ERR("%s: mode %d without its bin edges", who, mode);
         return NBK_ERR_ARG;
     }
     const int64_t nb = (int64_t)nb0 * (j1 - j0);
@@ -444,18 +464,13 @@ extern "C" int nbk_pairs_count_f64(const double* pos1, const double* w1,
 
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = count_lds_bytes(mode, nb0, j1 - j0, a.ncopy);
-    if (mode == 0) {
-        raise_lds(reinterpret_cast<const void*>(&kpairs_count<0>), lds);
-        hipLaunchKernelGGL(kpairs_count<0>, dim3((uint32_t)nblocks),
-                           dim3(PAIRS_THREADS), lds, s, a);
-    } else if (mode == 1) {
-        raise_lds(reinterpret_cast<const void*>(&kpairs_count<1>), lds);
-        hipLaunchKernelGGL(kpairs_count<1>, dim3((uint32_t)nblocks),
-                           dim3(PAIRS_THREADS), lds, s, a);
-    } else {
-        raise_lds(reinterpret_cast<const void*>(&kpairs_count<2>), lds);
-        hipLaunchKernelGGL(kpairs_count<2>, dim3((uint32_t)nblocks),
-                           dim3(PAIRS_THREADS), lds, s, a);
+    switch (mode) {
+    case 0: launch_count<0>(a, nblocks, lds, s); break;
+    case 1: launch_count<1>(a, nblocks, lds, s); break;
+    case 2: launch_count<2>(a, nblocks, lds, s); break;
+    case 3: launch_count<3>(a, nblocks, lds, s); break;
+    case 4: launch_count<4>(a, nblocks, lds, s); break;
+    default: launch_count<5>(a, nblocks, lds, s); break;
     }
     NBK_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(kpairs_reduce, dim3((uint32_t)((nb + 255) / 256)),
@@ -465,4 +480,80 @@ extern "C" int nbk_pairs_count_f64(const double* pos1, const double* w1,
                        wsum, xsum);
     NBK_CHECK_HIP(hipGetLastError());
     return NBK_OK;
+}
+
+}  // namespace
+
+extern "C" int nbk_pairs_cell_count_f64(const double* pos_aos, int64_t n,
+                                        int chunk, const double origin[3],
+                                        const double inv_cell[3],
+                                        const int ncell[3], int* mat,
+                                        void* stream)
+{
+    const char* who = "nbk_pairs_cell_count_f64";
+    PairsCellKey g;
+    int64_t ncells;
+    const int rc = make_grid(who, origin, inv_cell, ncell, &g, &ncells);
+    if (rc != NBK_OK) return rc;
+    return countsort_count<PairsCellKey, false>(who, pos_aos, n, chunk, g,
+                                                ncells, mat, nullptr,
+                                                stream);
+}
+
+extern "C" int nbk_pairs_cell_scatter_f64(const double* pos_aos,
+                                          const double* weight, int64_t n,
+                                          int chunk, const double origin[3],
+                                          const double inv_cell[3],
+                                          const int ncell[3],
+                                          const int* bases,
+                                          double* pos_out, double* w_out,
+                                          void* stream)
+{
+    const char* who = "nbk_pairs_cell_scatter_f64";
+    PairsCellKey g;
+    int64_t ncells;
+    const int rc = make_grid(who, origin, inv_cell, ncell, &g, &ncells);
+    if (rc != NBK_OK) return rc;
+    return countsort_scatter(who, pos_aos, weight, n, chunk, g, ncells,
+                             bases, n, pos_out, w_out, stream);
+}
+
+extern "C" int nbk_pairs_max_bins(void) { return NBK_PAIRS_MAX_BINS; }
+
+extern "C" int nbk_pairs_count_f64(const double* pos1, const double* w1,
+                                   const int* start1, int64_t n1,
+                                   const double* pos2, const double* w2,
+                                   const int* start2, int64_t n2,
+                                   int autocorr, const int ncell[3],
+                                   const double box[3], int periodic,
+                                   int mode, const double* edges0_sq,
+                                   int nb0, const double* edges1, int nb1,
+                                   int j0, int j1, int nblocks,
+                                   void* partials, int64_t* npairs,
+                                   double* wsum, double* xsum,
+                                   void* stream)
+{
+    return count_pairs("nbk_pairs_count_f64", 0, 2, pos1, w1, start1, n1,
+                       pos2, w2, start2, n2, autocorr, ncell, box,
+                       periodic, mode, edges0_sq, nb0, edges1, nb1, j0, j1,
+                       nblocks, partials, npairs, wsum, xsum, stream);
+}
+
+extern "C" int nbk_pairs_count_sky_f64(const double* pos1, const double* w1,
+                                       const int* start1, int64_t n1,
+                                       const double* pos2, const double* w2,
+                                       const int* start2, int64_t n2,
+                                       int autocorr, const int ncell[3],
+                                       int mode, const double* edges0_sq,
+                                       int nb0, const double* edges1,
+                                       int nb1, int j0, int j1, int nblocks,
+                                       void* partials, int64_t* npairs,
+                                       double* wsum, double* xsum,
+                                       void* stream)
+{
+    const double box[3] = {0.0, 0.0, 0.0};
+    return count_pairs("nbk_pairs_count_sky_f64", 3, 5, pos1, w1, start1,
+                       n1, pos2, w2, start2, n2, autocorr, ncell, box, 0,
+                       mode, edges0_sq, nb0, edges1, nb1, j0, j1, nblocks,
+                       partials, npairs, wsum, xsum, stream);
 }

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     'nbk_axpy_f64', 'nbk_scale_f64',
     'nbk_pairs_cell_count_f64', 'nbk_pairs_cell_scatter_f64',
     'nbk_pairs_max_bins', 'nbk_pairs_count_f64',
+    'nbk_pairs_count_sky_f64',
 ]
 
 _lib = None
@@ -180,6 +181,16 @@ def _declare(lib):
                                         ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, c_void,
                                         c_void, c_void, c_void, c_void]
+    lib.nbk_pairs_count_sky_f64.restype = ctypes.c_int
+    lib.nbk_pairs_count_sky_f64.argtypes = [c_void, c_void, c_void, c_i64,
+                                            c_void, c_void, c_void, c_i64,
+                                            ctypes.c_int, c_int_p,
+                                            ctypes.c_int,
+                                            c_void, ctypes.c_int, c_void,
+                                            ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int,
+                                            c_void, c_void, c_void, c_void,
+                                            c_void]
 
 
 def load():

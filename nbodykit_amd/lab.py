@@ -28,8 +28,10 @@ from nbodykit_amd.algorithms.convpower import (ConvolvedFFTPower,
                                                FKPCatalog,
                                                FKPWeightFromNbar)
 from nbodykit_amd.algorithms.zhist import RedshiftHistogram
-from nbodykit_amd.algorithms.pair_counters import SimulationBoxPairCount
-from nbodykit_amd.algorithms.paircount_tpcf import SimulationBox2PCF
+from nbodykit_amd.algorithms.pair_counters import (SimulationBoxPairCount,
+                                                   SurveyDataPairCount)
+from nbodykit_amd.algorithms.paircount_tpcf import (SimulationBox2PCF,
+                                                    SurveyData2PCF)
 from nbodykit_amd import filters
 from nbodykit_amd.source.catalog.species import MultipleSpeciesCatalog
 from nbodykit_amd import io as IO
