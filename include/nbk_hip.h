@@ -492,6 +492,39 @@ int nbk_pairs_count_sky_f64(const double* pos1, const double* w1,
                             int64_t* npairs, double* wsum, double* xsum,
                             void* stream);
 
+/* ---- three-point correlation function ------------------------------
+ * Multipoles zeta_l(r1, r2) of the isotropic 3PCF of ONE cell-sorted
+ * catalogue with itself (the compute core of SimulationBox3PCF and
+ * SurveyData3PCF; reference nbodykit/algorithms/threeptcf.py): for every
+ * primary i and radial bin b
+ *   a_lm(b) = sum_j w_j Y_lm(d_ij / r_ij),  edges[b] < r_ij <= edges[b+1],
+ *   zeta_l(b1, b2) = 1 / (4 pi) sum_i w_i sum_{m=0..l} c_m
+ *                    Re[a_lm(b1) conj(a_lm(b2))],  c_0 = 1, c_m = 2,
+ * with orthonormal Y_lm, d = (p_j - p_i) + s * box per axis (s the periodic
+ * image of the neighbour cell, as in nbk_pairs_count_f64; `box` is not
+ * read when periodic = 0) and r^2 = (dx^2 + dy^2) + dz^2 compared with
+ * edges_sq (device, nbins + 1 SQUARED edges): bins are OPEN below and
+ * CLOSED above, the opposite of the pair counter, and a pair at r = 0 (the
+ * point itself, a duplicate) is in no bin.  pos / w / start / ncell are the
+ * output and grid of nbk_pairs_cell_*, the cell side >= the largest edge.
+ *
+ * Capacity: lmax <= nbk_3pcf_max_ell() = 15 and nbins <=
+ * nbk_3pcf_max_bins(lmax) (64 * nbins * (lmax + 1)(lmax + 2) / 2 bytes of
+ * LDS per wave; 0 for an lmax out of range); anything larger returns
+ * NBK_ERR_ARG before any launch.  The grid is `nblocks` persistent blocks;
+ * `partials` is scratch of nblocks * (lmax + 1) * nbins * (nbins + 1) / 2
+ * doubles (per-block sums, plain stores) that a second kernel adds in block
+ * order into zeta[(lmax + 1) * nbins * nbins], index (l * nbins + b1) *
+ * nbins + b2, all l <= lmax.  No atomics: the same sorted input and the
+ * same nblocks give the same bits. */
+int nbk_3pcf_max_ell(void);
+int nbk_3pcf_max_bins(int lmax);
+int nbk_3pcf_zeta_f64(const double* pos, const double* w, const int* start,
+                      int64_t n, const int ncell[3], const double box[3],
+                      int periodic, const double* edges_sq, int nbins,
+                      int lmax, int nblocks, double* partials, double* zeta,
+                      void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

@@ -6,3 +6,4 @@ from .convpower import ConvolvedFFTPower, FKPCatalog, FKPWeightFromNbar
 from .zhist import RedshiftHistogram
 from .pair_counters import SimulationBoxPairCount, SurveyDataPairCount
 from .paircount_tpcf import SimulationBox2PCF, SurveyData2PCF
+from .threeptcf import SimulationBox3PCF, SurveyData3PCF

@@ -4,7 +4,9 @@ passes over ``nbk_pairs_*`` (csrc/nbk_pairs.hip).  Replaces the
 Corrfunc.theory.DD / DDsmu / DDrppi calls of the reference's
 pair_counters/corrfunc/theory.py, and with ``sky=True`` the
 DDsmu_mocks / DDrppi_mocks / DDtheta_mocks calls of corrfunc/mocks.py
-(SurveyDataPairCount).  Everything here runs on the GPU; the
+(SurveyDataPairCount).  ``zeta_multipoles`` drives the 3PCF kernel
+``nbk_3pcf_zeta_f64`` (csrc/nbk_3pcf.hip) on the same grid and cell
+sort.  Everything here runs on the GPU; the
 only host transfers are the bounding box (non-periodic runs) and the
 finished histograms.
 """
@@ -161,6 +163,81 @@ def cell_sort(lib, pos, w, origin, inv_cell, ncell):
 def single_pass_capacity():
     """Total bins one count pass holds (NBK_PAIRS_MAX_BINS)."""
     return int(hiplib.load().nbk_pairs_max_bins())
+
+
+def threeptcf_limits(lmax=None):
+    """(largest multipole, bins that fit at ``lmax``) of nbk_3pcf_zeta_f64;
+    the bin capacity is None without ``lmax``.  Needs no GPU."""
+    lib = hiplib.load()
+    max_ell = int(lib.nbk_3pcf_max_ell())
+    if lmax is None:
+        return max_ell, None
+    return max_ell, int(lib.nbk_3pcf_max_bins(int(lmax)))
+
+
+def zeta_multipoles(pos, w, edges, lmax, box, periodic, info=None):
+    """
+    3PCF multipoles zeta_l(r1, r2), l = 0..lmax, of a device catalogue
+    with itself (csrc/nbk_3pcf.hip): a host array (lmax + 1, nbins, nbins).
+
+    pos: (n, 3) f64 CUDA rows, already wrapped into the box for a periodic
+    run; bins are open below and closed above.  The grid covers the box
+    (periodic) or the bounding box, its cells at least max(edges) wide.
+    ``info``, if a dict, receives the grid and the launch shape.
+    """
+    import torch
+    lib = hiplib.require()
+    edges = numpy.asarray(edges, dtype='f8')
+    nbins = len(edges) - 1
+    lmax = int(lmax)
+    max_ell, _ = threeptcf_limits()
+    if lmax < 0 or lmax > max_ell:
+        raise ValueError("multipoles must lie in [0, %d]" % max_ell)
+    cap = threeptcf_limits(lmax)[1]
+    if nbins < 1 or nbins > cap:
+        raise ValueError("at most %d bins at lmax = %d" % (cap, lmax))
+    rmax = float(numpy.max(edges))
+    n = int(pos.shape[0])
+
+    lo = hi = None
+    if not periodic:
+        if n:
+            lo, hi = pos.amin(dim=0).tolist(), pos.amax(dim=0).tolist()
+        else:
+            lo = hi = [0.0, 0.0, 0.0]
+    origin, inv_cell, ncell = make_grid(periodic, box, rmax, lo, hi)
+
+    with profiling.collect('3pcf_sort', units=n):
+        spos, sw, start = cell_sort(lib, pos, w, origin, inv_cell, ncell)
+
+    dev = torch.device('cuda')
+    esq = torch.as_tensor(edges * edges).to(dev)
+    # a persistent grid: the blocks a CU holds by their LDS (64 bytes per
+    # bin and (l, m) per wave, up to 4 waves) and by their registers (4-
+    # wave blocks at 4, 3, 2 waves per SIMD for lmax < 8, < 12, <= 15:
+    # DESIGN.md "Three-point correlation function")
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    nlm = (lmax + 1) * (lmax + 2) // 2
+    by_regs = 4 if lmax < 8 else 3 if lmax < 12 else 2
+    per_cu = max(1, min(by_regs,
+                        (150 * 1024) // (4 * 64 * nbins * nlm + 8192)))
+    nblocks = ncu * per_cu
+    nent = (lmax + 1) * nbins * (nbins + 1) // 2
+    partials = torch.empty(nblocks * nent, dtype=torch.float64, device=dev)
+    zeta = torch.empty((lmax + 1) * nbins * nbins, dtype=torch.float64,
+                       device=dev)
+    with profiling.collect('3pcf_zeta', units=n):
+        hiplib.check(lib.nbk_3pcf_zeta_f64(
+            hiplib.dptr(spos), hiplib.dptr(sw), hiplib.dptr(start), n,
+            hiplib.int_arr(ncell),
+            hiplib.f64_arr(box if periodic else [0.0, 0.0, 0.0]),
+            1 if periodic else 0, hiplib.dptr(esq), nbins, lmax, nblocks,
+            hiplib.dptr(partials), hiplib.dptr(zeta),
+            hiplib.cur_stream()), 'nbk_3pcf_zeta_f64')
+    if info is not None:
+        info.update(ncell=ncell, nblocks=nblocks,
+                    start=start.cpu().numpy())
+    return zeta.cpu().numpy().reshape(lmax + 1, nbins, nbins)
 
 
 def count_pairs(mode, pos1, w1, pos2, w2, edges, edges2, box, periodic,

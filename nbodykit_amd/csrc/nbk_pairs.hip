@@ -35,6 +35,7 @@
 // (reachable when edges[0] = 0) has no mu and is dropped in mode 1; modes
 // 0 and 2 count it (q = 0, pi = 0).
 #include "nbk_countsort.h"
+#include "nbk_cells.h"
 
 namespace {
 
@@ -98,27 +99,6 @@ struct PairsArgs {
     double* part_w;
     double* part_x;
 };
-
-// one axis of the neighbour walk: offset d = -1, 0, +1 of cell c
-__device__ __forceinline__ bool neighbour_axis(int c, int d, int n,
-                                               int periodic, double L,
-                                               int* c2, double* shift) {
-    const int raw = c + d;
-    if (raw >= 0 && raw < n) {
-        *c2 = raw;
-        *shift = 0.0;
-        return true;
-    }
-    if (!periodic) return false;
-    if (raw < 0) {
-        *c2 = raw + n;
-        *shift = -L;
-    } else {
-        *c2 = raw - n;
-        *shift = L;
-    }
-    return true;
-}
 
 // modes without a second dimension
 __host__ __device__ constexpr bool mode_is_1d(int mode) {

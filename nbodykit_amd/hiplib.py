@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     'nbk_pairs_cell_count_f64', 'nbk_pairs_cell_scatter_f64',
     'nbk_pairs_max_bins', 'nbk_pairs_count_f64',
     'nbk_pairs_count_sky_f64',
+    'nbk_3pcf_max_ell', 'nbk_3pcf_max_bins', 'nbk_3pcf_zeta_f64',
 ]
 
 _lib = None
@@ -191,6 +192,15 @@ def _declare(lib):
                                             ctypes.c_int, ctypes.c_int,
                                             c_void, c_void, c_void, c_void,
                                             c_void]
+    lib.nbk_3pcf_max_ell.restype = ctypes.c_int
+    lib.nbk_3pcf_max_ell.argtypes = []
+    lib.nbk_3pcf_max_bins.restype = ctypes.c_int
+    lib.nbk_3pcf_max_bins.argtypes = [ctypes.c_int]
+    lib.nbk_3pcf_zeta_f64.restype = ctypes.c_int
+    lib.nbk_3pcf_zeta_f64.argtypes = [c_void, c_void, c_void, c_i64,
+                                      c_int_p, c_f64_p, ctypes.c_int,
+                                      c_void, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, c_void, c_void, c_void]
 
 
 def load():
