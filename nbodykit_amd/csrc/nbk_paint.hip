@@ -317,6 +317,201 @@ __global__ void kpaint_tiled(const double* __restrict__ px,
     }
 }
 
+// ---- register-resident z-FFT of one tile row (kpaint_gather, DOFFT) ----
+//
+// One wave transforms one row of m = 64 R packed complex points
+// (R = 1, 2, 4, 8: n2 = 128 ... 1024) in place in the row's LDS, holding
+// the points in registers, max(R, 8) per lane, between the passes:
+//
+//   m = R * 8 * 8.  Input index n = lane + 64 j, output index
+//   k = 8R c + R d + k1   (j, k1 < R;  lane = 8a + b;  a, b, c, d < 8)
+//
+//   pass 1  lane            reads z[lane + 64 j] (natural order: no
+//                           bit-reversal pass), R-point DFT over j -> k1,
+//                           times W_m^(lane k1)
+//   pass 2  lane' = 8k1 + b 8-point DFT over a -> d, times W_64^(b d)
+//   pass 3  lane" = Rd + k1 8-point DFT over b -> c, written to
+//                           z[lane" + 8R c] = z[k]: natural order
+//
+// Passes 2 and 3 run on the first 8R lanes (all 64 at n2 = 1024).  The
+// butterflies are straight-line register code whose only constants are
+// +-sqrt(1/2); the inter-pass twiddles depend on the lane alone and are
+// loaded once per block (zfft_load_twiddles).  A row makes 4 LDS round
+// trips: read, two exchanges, natural-order write (+ the split's reads).
+//
+// Exchange slots (16-byte units, relative to the row), all within
+// [0, m) — the exchanges are in place:
+//   exchange 1: slot(k1, l) = 64 k1 + (l ^ 8 (k1>>1 & 1)),   l = 8a + b
+//   exchange 2: slot(b, q)  = 8R b + (q ^ b),                q = Rd + k1
+// LDS banking on gfx950: a 16-byte read is served in four groups of 16
+// lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31}, the same + 32) over 16
+// slots; a 16-byte write in eight groups of 8 consecutive lanes over 8
+// slots.  Writes of exchange 1 (fixed k1), reads of exchange 2 (fixed b)
+// and the final writes (fixed c) put consecutive lanes on consecutive
+// slots, XORed with a constant below 16: conflict-free.  Reads of
+// exchange 1 (fixed a, lane' = 8k1 + b): slot mod 16 is
+// b + 8 (a ^ (k1>>1)), and each read group holds b = 0..3 and b = 4..7
+// once for an even and once for an odd k1>>1 — 16 distinct slots.
+// Writes of exchange 2 (fixed d, lane' = 8k1 + b): within a group k1 is
+// fixed and slot mod 8 = (const ^ b), b = 0..7 — 8 distinct slots.
+// Every exchange is conflict-free (1-way) for R = 1, 2, 4, 8, counted by
+// enumeration of the groups above.
+//
+// A wave owns its row: the lanes run in lockstep and LDS operations
+// complete in program order, so the passes need no block barrier; the
+// wave_barrier pins the compiler's schedule across the cross-lane
+// dependences, as in the LDS radix-4 network this replaces.
+typedef double nbk_f64x2 __attribute__((ext_vector_type(2)));
+
+// 16-byte LDS access of one complex point (the rows are 16-byte aligned)
+__device__ __forceinline__ cdouble zfft_ld(const cdouble* z, int i) {
+    const nbk_f64x2 v = *reinterpret_cast<const nbk_f64x2*>(z + i);
+    return {v.x, v.y};
+}
+__device__ __forceinline__ void zfft_st(cdouble* z, int i, cdouble a) {
+    const nbk_f64x2 v = {a.re, a.im};
+    *reinterpret_cast<nbk_f64x2*>(z + i) = v;
+}
+
+// forward R-point DFT in registers, natural order in and out
+template <int R>
+__device__ __forceinline__ void zfft_butterfly(cdouble (&v)[R]) {
+    static_assert(R == 1 || R == 2 || R == 4 || R == 8, "radix");
+    if constexpr (R == 2) {
+        const cdouble a = v[0], b = v[1];
+        v[0] = cadd(a, b);
+        v[1] = csub(a, b);
+    } else if constexpr (R == 4) {
+        const cdouble s0 = cadd(v[0], v[2]), s1 = csub(v[0], v[2]);
+        const cdouble s2 = cadd(v[1], v[3]), s3 = csub(v[1], v[3]);
+        const cdouble is3 = {s3.im, -s3.re};              // -i * s3
+        v[0] = cadd(s0, s2);
+        v[1] = cadd(s1, is3);
+        v[2] = csub(s0, s2);
+        v[3] = csub(s1, is3);
+    } else if constexpr (R == 8) {
+        cdouble e[4] = {v[0], v[2], v[4], v[6]};
+        cdouble o[4] = {v[1], v[3], v[5], v[7]};
+        zfft_butterfly<4>(e);
+        zfft_butterfly<4>(o);
+        constexpr double h = 0.70710678118654752440;       // sqrt(1/2)
+        // o[k] *= W_8^k
+        o[1] = {(o[1].re + o[1].im) * h, (o[1].im - o[1].re) * h};
+        o[2] = {o[2].im, -o[2].re};
+        o[3] = {(o[3].im - o[3].re) * h, -(o[3].re + o[3].im) * h};
+        #pragma unroll
+        for (int k = 0; k < 4; k++) {
+            v[k] = cadd(e[k], o[k]);
+            v[k + 4] = csub(e[k], o[k]);
+        }
+    }
+}
+
+// the inter-pass twiddles of one lane; they depend on the lane and n2
+// only and serve every row the wave transforms.  Only the powers 1, 2
+// and 4 of each pass's base twiddle are kept (24 VGPRs, not 56: the
+// n2 = 1024 instance has to fit 128 with its 8 points and the
+// butterfly's temporaries); zfft_twiddle forms the other powers as
+// products where it uses them.
+struct zfft_twiddles {
+    cdouble w1[3];    // W_m^(lane k1), k1 = 1, 2, 4 (those below R)
+    cdouble w2[3];    // W_64^(b d), b = lane & 7, d = 1, 2, 4
+};
+
+// v[k] *= w^k, k = 1..N-1, from p = (w, w^2, w^4)
+template <int N>
+__device__ __forceinline__ void zfft_twiddle(cdouble (&v)[N],
+                                             const cdouble (&p)[3]) {
+    v[1] = cmul(v[1], p[0]);
+    if constexpr (N > 2) {
+        const cdouble p3 = cmul(p[0], p[1]);
+        v[2] = cmul(v[2], p[1]);
+        v[3] = cmul(v[3], p3);
+        if constexpr (N > 4) {
+            v[4] = cmul(v[4], p[2]);
+            v[5] = cmul(v[5], cmul(p[0], p[2]));
+            v[6] = cmul(v[6], cmul(p[1], p[2]));
+            v[7] = cmul(v[7], cmul(p3, p[2]));
+        }
+    }
+}
+
+template <int LOGM>
+__device__ __forceinline__ void zfft_load_twiddles(
+    zfft_twiddles& tw, const cdouble* __restrict__ table /* W_n2,
+        entries 0..m */, int lane)
+{
+    constexpr int R = 1 << (LOGM - 6), m = 64 * R;
+    // W_n2^e for 0 <= e < n2 from the half table: W^(e) = -W^(e - m)
+    auto W = [&](int e) -> cdouble {
+        const cdouble w = table[e > m ? e - m : e];
+        return e > m ? cdouble{-w.re, -w.im} : w;
+    };
+    #pragma unroll
+    for (int i = 0; i < 3; i++) {
+        if ((1 << i) < R) tw.w1[i] = W(2 * lane << i);
+        tw.w2[i] = W(2 * R * (lane & 7) << i);
+    }
+}
+
+// forward complex FFT of the m points z[0..m), natural order in and out
+template <int LOGM>
+__device__ __forceinline__ void zfft_row(cdouble* z, int lane,
+                                         zfft_twiddles tw)
+{
+    constexpr int R = 1 << (LOGM - 6), L2 = 8 * R;
+    // The lane and the kept twiddle powers pass through an empty asm
+    // once per row: what is derived from them (the exchange slots, the
+    // twiddle products) is then computed where it is used instead of
+    // being hoisted out of the caller's row loop into some 50 more
+    // registers, which the n2 = 1024 instance does not have.
+    asm volatile("" : "+v"(lane));
+    #pragma unroll
+    for (int i = 0; i < 3; i++) {
+        if ((1 << i) < R)
+            asm volatile("" : "+v"(tw.w1[i].re), "+v"(tw.w1[i].im));
+        asm volatile("" : "+v"(tw.w2[i].re), "+v"(tw.w2[i].im));
+    }
+    if constexpr (R > 1) {
+        // pass 1 (at R = 1 it and its exchange are the identity)
+        cdouble v[R];
+        #pragma unroll
+        for (int j = 0; j < R; j++) v[j] = zfft_ld(z, lane + 64 * j);
+        zfft_butterfly<R>(v);
+        zfft_twiddle<R>(v, tw.w1);
+        __builtin_amdgcn_wave_barrier();
+        #pragma unroll
+        for (int k1 = 0; k1 < R; k1++)
+            zfft_st(z, 64 * k1 + (lane ^ (8 * ((k1 >> 1) & 1))), v[k1]);
+        __builtin_amdgcn_wave_barrier();
+    }
+    const bool active = (L2 == 64) || lane < L2;
+    if (active) {
+        // pass 2
+        const int k1 = lane >> 3, b = lane & 7;
+        const int base = 64 * k1 + (b ^ (8 * ((k1 >> 1) & 1)));
+        cdouble u[8];
+        #pragma unroll
+        for (int a = 0; a < 8; a++) u[a] = zfft_ld(z, base ^ (8 * a));
+        zfft_butterfly<8>(u);
+        zfft_twiddle<8>(u, tw.w2);
+        #pragma unroll
+        for (int d = 0; d < 8; d++)
+            zfft_st(z, L2 * b + ((R * d + k1) ^ b), u[d]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (active) {
+        // pass 3
+        cdouble s[8];
+        #pragma unroll
+        for (int b = 0; b < 8; b++) s[b] = zfft_ld(z, L2 * b + (lane ^ b));
+        zfft_butterfly<8>(s);
+        #pragma unroll
+        for (int c = 0; c < 8; c++) zfft_st(z, lane + L2 * c, s[c]);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
 // OWNERSHIP-GATHER paint for cell-sorted input with a row table
 // (nbk_bucket_fine_f64's rowtab): each block owns an exclusive mesh
 // tile of RG y-rows x full z of ONE x-plane, accumulates every deposit
@@ -327,15 +522,19 @@ __global__ void kpaint_tiled(const double* __restrict__ px,
 // deposits are LDS ds_add_f64 and the HBM traffic is ~2.1x the particle
 // reads plus one mesh write.
 // DOFFT: after the deposits the tile's rows (full z-lines) are
-// transformed in place (packed-real radix-2, identical math to
-// kfft_r2c_z) and the z half-spectrum is written directly — the real
+// transformed in place (packed-real complex FFT + untwiddle split as
+// kfft_r2c_z; zfft_row above for n2 = 128 ... 1024, the LDS radix-4
+// network otherwise) and the z half-spectrum is written directly — the real
 // mesh never touches HBM.  The row stride is padded (+4 doubles) so the
 // butterflies of different rows land in different LDS banks.
 // PT: compile-time plane count when > 0 (PT=1 restores the
 // single-plane kernel's indexing with zero multi-plane overhead — the
 // CIC path is VALU+read balanced and pays for every extra op);
 // PT=0 = runtime P.
-template <int WINDOW, bool DOFFT, int PT>
+// ZF (DOFFT only): log2(n2/2) when the row transform is the
+// register-resident zfft_row (n2 = 128 ... 1024), 0 = the LDS radix-4
+// network (every other length).
+template <int WINDOW, bool DOFFT, int PT, int ZF>
 __global__ void kpaint_gather(const double* __restrict__ px,
                               const double* __restrict__ py,
                               const double* __restrict__ pz,
@@ -365,7 +564,8 @@ __global__ void kpaint_gather(const double* __restrict__ px,
 {
     constexpr int SUP = window_support<WINDOW>();
     if (PT > 0) P = PT;                  // compile-time plane count
-    extern __shared__ double tile[];      // P * RG * (n2 [+4]) doubles
+    // P * RG * (n2 [+4]) doubles; rows start on 16 bytes
+    extern __shared__ __attribute__((aligned(16))) double tile[];
     const int64_t sp = DOFFT ? n2 + 4 : n2;   // padded row stride
     const int64_t tiles_per_plane = n1 / RG;
     // block owns P consecutive x-planes x RG y-rows: a source plane
@@ -655,17 +855,21 @@ __global__ void kpaint_gather(const double* __restrict__ px,
         return;
     }
 
-    // ---- fused forward z-FFT, one WAVE per tile row (math identical
-    // to kfft_r2c_z: packed-real radix-2 DIT + untwiddle split).  A
-    // wave owns a whole row, so the stage ordering needs no block
+    // ---- fused forward z-FFT, one WAVE per tile row (packed-real
+    // complex FFT of m = n2/2 points + untwiddle split, as kfft_r2c_z).
+    // A wave owns a whole row, so the stage ordering needs no block
     // syncs — CDNA wave64 executes in lockstep and LDS ops complete in
     // program order; the wave_barrier only pins the compiler's
-    // scheduling across the cross-lane dependences. ----
+    // scheduling across the cross-lane dependences.  ZF > 0: the
+    // complex FFT is zfft_row, its twiddles loaded here once for all
+    // the rows of the wave. ----
     const int m = (int)(n2 >> 1);
     const int bits = 31 - __clz((unsigned)m);
     const int lane = t & 63;
     const int wave = t >> 6;
     const int nw = T >> 6;
+    zfft_twiddles ztw;
+    if constexpr (ZF > 0) zfft_load_twiddles<ZF>(ztw, table, lane);
 
     for (int r = wave; r < P * RG; r += nw) {
         const int64_t pl = (PT == 1) ? 0 : r / RG;
@@ -674,6 +878,9 @@ __global__ void kpaint_gather(const double* __restrict__ px,
             + ((px0 - x0 + pl) * n1 + r0 + rr) * (m + 1);
         cdouble* z = (cdouble*)&tile[(int64_t)r * sp];
 
+        if constexpr (ZF > 0) {
+            zfft_row<ZF>(z, lane, ztw);
+        } else {
         for (int j = lane; j < m; j += 64) {
             const int jr = nbk_bitrev(j, bits);
             if (j < jr) {
@@ -732,6 +939,7 @@ __global__ void kpaint_gather(const double* __restrict__ px,
                 __builtin_amdgcn_wave_barrier();
             }
         }
+        }   // ZF == 0
 
         // untwiddle split: X[k] = E[k] + W_n2^k O[k], k = 0..m, written
         // straight to the z half-spectrum
@@ -828,6 +1036,21 @@ bool with_window(int window, F&& f) {
         f(std::integral_constant<int, NBK_WINDOW_PCS>{}); return true;
     }
     return false;
+}
+
+// The one place the fused z-FFT's length becomes a template argument:
+// calls f(std::integral_constant<int, ZF>{}) with ZF = log2(n2/2) for
+// the lengths zfft_row holds in registers (m/64 <= 8 points per lane,
+// m >= 64), ZF = 0 (the LDS radix-4 network) for every other n2.
+template <class F>
+void with_zfft(int64_t n2, F&& f) {
+    switch (n2) {
+    case 128:  f(std::integral_constant<int, 6>{}); return;
+    case 256:  f(std::integral_constant<int, 7>{}); return;
+    case 512:  f(std::integral_constant<int, 8>{}); return;
+    case 1024: f(std::integral_constant<int, 9>{}); return;
+    }
+    f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace
@@ -1035,10 +1258,12 @@ static int paint_gather_launch(const char* who, const double* pos,
     const int64_t grid = (nx_local / P) * (n1 / RG);
     const size_t lds = (size_t)P * RG * (n2 + pad) * sizeof(double);
     hipStream_t s = (hipStream_t)stream;
-    // PT: the kernel's compile-time plane count (1, or 0 = runtime P)
-    auto launch = [&](auto w, auto pt) {
+    // PT: the kernel's compile-time plane count (1, or 0 = runtime P);
+    // ZF: the fused z-FFT's row transform (with_zfft)
+    auto launch = [&](auto w, auto pt, auto zf) {
         auto* kernel = &kpaint_gather<decltype(w)::value, DOFFT,
-                                      decltype(pt)::value>;
+                                      decltype(pt)::value,
+                                      decltype(zf)::value>;
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute(
                 reinterpret_cast<const void*>(kernel),
@@ -1052,8 +1277,12 @@ static int paint_gather_launch(const char* who, const double* pos,
                            nbk_paint_phases());
     };
     with_window(window, [&](auto w) {
-        if (P == 1) launch(w, std::integral_constant<int, 1>{});
-        else launch(w, std::integral_constant<int, 0>{});
+        auto go = [&](auto zf) {
+            if (P == 1) launch(w, std::integral_constant<int, 1>{}, zf);
+            else launch(w, std::integral_constant<int, 0>{}, zf);
+        };
+        if constexpr (DOFFT) with_zfft(n2, go);
+        else go(std::integral_constant<int, 0>{});
     });
     NBK_CHECK_HIP(hipGetLastError());
     return NBK_OK;
