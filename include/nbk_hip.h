@@ -525,6 +525,82 @@ int nbk_3pcf_zeta_f64(const double* pos, const double* w, const int* start,
                       int lmax, int nblocks, double* partials, double* zeta,
                       void* stream);
 
+/* friends-of-friends -------------------------------------------------
+ * The replacement for kdcount.cluster.fof under
+ * nbodykit/algorithms/fof.py: two particles are friends iff
+ *   r2 = (dx*dx + dy*dy) + dz*dz <= ll_sq,  d = (p_i - p_j) - s * box
+ * per axis (s the periodic image of the neighbour cell, as in
+ * nbk_pairs_count_f64; zero separation links), and a group is a connected
+ * component of that relation.  f64 throughout.
+ *
+ * Cell grid, two levels: ncell[a] = ncoarse[a] * fine[a] cells per axis
+ * with ncoarse[0]*ncoarse[1]*ncoarse[2] <= 40960 and
+ * fine[0]*fine[1]*fine[2] <= 40960 (one LDS histogram each) and fewer
+ * than 2^31 cells in all.  The fine cell of a particle is
+ * c[a] = clamp(floor((p - origin) * inv_cell), 0, ncell - 1) per axis; its
+ * coarse cell is the integer c[a] / fine[a] and its sub-cell c[a] % fine[a]
+ * (never a second floor).  Cells are numbered BLOCK-MAJOR:
+ *   cell = coarse_id * nfine + sub_id,  nfine = fine[0]*fine[1]*fine[2],
+ *   coarse_id = ((c[0]/fine[0]) * ncoarse[1] + c[1]/fine[1]) * ncoarse[2]
+ *               + c[2]/fine[2],
+ *   sub_id = ((c[0]%fine[0]) * fine[1] + c[1]%fine[1]) * fine[2]
+ *            + c[2]%fine[2].
+ * The caller picks a cell side >= the linking length.
+ *
+ * Coarse sort (the count-matrix scheme of nbk_xsort_*, with its n / chunk
+ * requirements, keyed by coarse_id): nbk_fof_cell_count_f64 ->
+ * nbk_scan_matrix_i32(mat, nchunks, ncoarse_all, ...) ->
+ * nbk_fof_cell_scatter_f64, which places the (n, 3) row-major positions
+ * and the f64 column `index` (the original particle index, exact in a
+ * double) into SoA pos_out = x[n] y[n] z[n] and index_out[n]; the scan's
+ * bucket_bases (ncoarse_all + 1) is the coarse start table. */
+int nbk_fof_cell_count_f64(const double* pos_aos, int64_t n, int chunk,
+                           const double origin[3], const double inv_cell[3],
+                           const int ncoarse[3], const int fine[3],
+                           int* mat, void* stream);
+int nbk_fof_cell_scatter_f64(const double* pos_aos, const double* index,
+                             int64_t n, int chunk, const double origin[3],
+                             const double inv_cell[3], const int ncoarse[3],
+                             const int fine[3], const int* bases,
+                             double* pos_out, double* index_out,
+                             void* stream);
+/* Fine pass: one block per coarse cell over the coarse-sorted SoA planes
+ * and coarse_start.  Writes the cell-sorted SoA pos_out, the int32
+ * original index index_out[n] and the fine start table
+ * fine_start[ncells + 1] (exclusive, [ncells] = n), all in block-major cell
+ * order; order inside a cell is arbitrary.  No global atomics; correct
+ * for a coarse cell of any occupancy from 0 to n.  n = 0 only zeroes
+ * fine_start. */
+int nbk_fof_fine_sort_f64(const double* pos_soa, const double* index,
+                          int64_t n, const double origin[3],
+                          const double inv_cell[3], const int ncoarse[3],
+                          const int fine[3], const int* coarse_start,
+                          double* pos_out, int* index_out, int* fine_start,
+                          void* stream);
+/* Link: unites every pair of friends in `parent` (n int32, the identity
+ * on entry; on return a forest with parent[k] <= k whose trees are the
+ * groups).  One thread per sorted particle tests the lower sorted indices
+ * of its <= 27 neighbour (cell, shift)s, so each unordered pair is tested
+ * once per image; with fewer than 3 cells on a periodic axis a pair may
+ * be in range under two shifts, and the second union is a no-op.  Unions
+ * hook the larger root under the smaller with an agent-scope 32-bit
+ * compare-and-swap; all other accesses to `parent` are agent-scope relaxed
+ * atomics.  No fences, no grid barrier, no waiting: every loop is bounded
+ * by n even on a corrupt array.  *err (device int, zeroed by the caller)
+ * is set when a parent is not below its child; box is not read when
+ * periodic = 0. */
+int nbk_fof_link_f64(const double* pos_soa, const int* fine_start, int64_t n,
+                     const int ncoarse[3], const int fine[3],
+                     const double box[3], int periodic, double ll_sq,
+                     int* parent, int* err, void* stream);
+/* Flatten (a separate launch): root[i] = the root of i in `parent`, into
+ * a separate array, with the same bounded walk and the same *err word.
+ * Waits for the stream, reads *err back and returns NBK_ERR_ARG when it
+ * is set (by this pass or by the link before it); root[i] = -1 where the
+ * walk gave up. */
+int nbk_fof_flatten_i32(const int* parent, int64_t n, int* root, int* err,
+                        void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

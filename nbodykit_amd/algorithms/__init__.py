@@ -7,3 +7,4 @@ from .zhist import RedshiftHistogram
 from .pair_counters import SimulationBoxPairCount, SurveyDataPairCount
 from .paircount_tpcf import SimulationBox2PCF, SurveyData2PCF
 from .threeptcf import SimulationBox3PCF, SurveyData3PCF
+from .fof import FOF

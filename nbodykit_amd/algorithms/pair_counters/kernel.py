@@ -96,7 +96,8 @@ def candidate_pairs(start1, start2, ncell, periodic):
 def to_device_columns(position, weight, axes_order):
     """numpy (any float width / byte order) or torch columns -> f64 CUDA
     tensors, position as contiguous (n, 3) rows with the line of sight
-    last.  Device columns stay on the device."""
+    last.  Device columns stay on the device.  ``weight`` may be None
+    (positions only): the second result is then None."""
     import torch
 
     def as_tensor(col):
@@ -111,6 +112,8 @@ def to_device_columns(position, weight, axes_order):
     if pos.ndim != 2 or pos.shape[1] != 3:
         raise ValueError("position column must have shape (N, 3)")
     pos = pos[:, list(axes_order)].contiguous()
+    if weight is None:
+        return pos, None
     w = as_tensor(weight).to(device='cuda', dtype=torch.float64)
     w = w.contiguous()
     if w.shape != (pos.shape[0],):

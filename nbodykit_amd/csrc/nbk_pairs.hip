@@ -43,13 +43,6 @@ namespace {
 constexpr int PAIRS_TILE = 256;
 constexpr int PAIRS_THREADS = 256;
 
-__device__ __forceinline__ int cell_axis(double x, double origin,
-                                         double inv_cell, int n) {
-    int c = (int)floor((x - origin) * inv_cell);
-    c = c < 0 ? 0 : c;
-    return c >= n ? n - 1 : c;
-}
-
 // the cell sort's key: the clamped cell id
 struct PairsCellKey {
     typedef int index_t;
