@@ -361,9 +361,14 @@ int nbk_power_bin_f64(const double* c1, const double* c2, double volume,
  * SQUARED k edges (as in nbk_bin_power_f64); out_sums is the contiguous
  * [xsum|musum|Nsum|ysum] block of (nx_edges+1)*(nmu_edges+1) doubles
  * each (ysum: nell planar re/im pairs).  nmesh[0] must be a power of
- * two in [8, 4096]; fails with NBK_ERR_UNSUPPORTED when the histogram +
- * FFT tile exceed the 160 KiB LDS (callers fall back to the unfused
- * sequence). */
+ * two, at least 8 and at most 2048 (1024 with data2, which doubles the
+ * tile): the narrowest FFT tile (32 B per x point and field) and the
+ * n0-entry tables of a longer line cannot fit the 160 KiB LDS beside any
+ * histogram, so larger sizes return NBK_ERR_UNSUPPORTED.  So does any
+ * size whose histograms + edges + tables + narrowest tile exceed the
+ * 160 KiB less the 4 KiB reserved for the kernel's static arrays; nothing
+ * is launched and out_sums is left untouched (callers fall back to the
+ * unfused sequence).  At most 8 multipoles (NBK_ERR_ARG beyond). */
 /* data2: NULL for a plain auto power; for an INTERLACED mesh the
  * half-cell-shifted paint's pre-x-pass field — both tiles are FFT'd
  * and combined as c = a/2 + b/2 exp(i k.H/2) before compensation and

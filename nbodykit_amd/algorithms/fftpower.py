@@ -642,7 +642,8 @@ def _xbin_ok(mesh, Nmesh):
 def _xbin_lds_fits(n0, nx_edges, nmu_edges, nell, il=False):
     """Mirror of nbk_fft_x_bin_f64's LDS budget: histograms + edge
     arrays + compensation (+ interlace phase) tables + the TI=1 FFT
-    tile(s) must fit the gfx950 160 KiB LDS, and the register pipeline
+    tile(s) must fit the gfx950 160 KiB LDS less the 4 KiB the launcher
+    reserves for the kernel's static arrays, and the register pipeline
     caps n0*TI (the kernel itself would return NBK_ERR_UNSUPPORTED;
     gate here so the standard path is taken without a failed
     launch)."""
@@ -653,7 +654,9 @@ def _xbin_lds_fits(n0, nx_edges, nmu_edges, nell, il=False):
         if n0 > 2048:
             return False
     nbufs = 2 if il else 1
-    return fixed + nbufs * n0 * 2 * 16 <= 160 * 1024  # TI=1, pitch 2
+    # the kernel's static arrays share the 160 KiB (NBK_XBIN_STATIC_LDS)
+    budget = 160 * 1024 - 4096
+    return fixed + nbufs * n0 * 2 * 16 <= budget      # TI=1, pitch 2
 
 
 def _project_power_xbin(tensor, tensor2, pm, n_inner, comp1, volume,

@@ -14,13 +14,20 @@
 // beyond the last k-edge before touching field data.  Line-grouped
 // block mapping keeps the expensive index math per line, with the
 // digitize edges staged through LDS.  Histograms accumulate in LDS
-// (up to 160 KiB via hipFuncSetAttribute) and flush once; the
-// global-atomic fallback serves grids beyond that.
+// (up to 160 KiB less the kernels' static arrays, via
+// hipFuncSetAttribute) and flush once; the global-atomic fallback serves
+// grids beyond that.
 #include "nbk_common.h"
 
 namespace {
 
 #define NBK_MAX_ELL 8
+
+// LDS the binning kernels declare statically (the per-line stages: 1056 B
+// in kbin_run, 128 B in kbin), kept out of the dynamic budget: a launch
+// whose static + dynamic LDS exceeds the CU's 160 KiB is invalid
+#define NBK_BIN_STATIC_LDS 2048
+#define NBK_BIN_LDS_BUDGET (160 * 1024 - NBK_BIN_STATIC_LDS)
 
 struct BinArgs {
     int64_t n0, n1, n2;        // global REAL mesh (n2 = full length)
@@ -139,6 +146,9 @@ __global__ void kbin(const double* __restrict__ data,
     const int64_t nlines = A.d0 * A.d1;
     constexpr int NL = 8;
     __shared__ double lf0[NL], lf1[NL];
+    // (any further __shared__ array of this kernel must be added here)
+    static_assert(2 * sizeof(double[NL]) <= NBK_BIN_STATIC_LDS,
+                  "kbin: static LDS above the launcher's reserve");
     const int64_t ngroups = (nlines + NL - 1) / NL;
     for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const int64_t line0 = grp * NL;
@@ -341,6 +351,10 @@ __global__ void kbin_run(const double* __restrict__ data,
     constexpr int R = 16;
     __shared__ double lsxy[NL], ldot[NL], lc1[NL], lc2[NL];
     __shared__ unsigned char lz0[NL];
+    // (any further __shared__ array of this kernel must be added here)
+    static_assert(4 * sizeof(double[NL]) + sizeof(unsigned char[NL])
+                  <= NBK_BIN_STATIC_LDS,
+                  "kbin_run: static LDS above the launcher's reserve");
     const int64_t ngroups = (nlines + NL - 1) / NL;
     for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         const int64_t line0 = grp * NL;
@@ -649,14 +663,16 @@ static int launch_bin(const double* d1, const double* d2, BinArgs& A,
     // default need the attribute raised once.  The per-block histogram is
     // worth ~1 occupancy: the global-atomic fallback costs seconds at
     // 1024^3 x Nmu=5 (every element 5+ HBM atomics).
-    const bool fast = (A.a2 == 2) && !real_field;
+    // kbin_run: edges + the two z compensation tables always live in
+    // LDS (the histograms do when they fit); tables beyond the budget go
+    // to the general kernel, which can read the edges from global memory
+    const size_t tab = ((size_t)nx_edges + nmu_edges + 2 * A.d2)
+                       * sizeof(double);
+    const bool fast = (A.a2 == 2) && !real_field
+                      && tab <= NBK_BIN_LDS_BUDGET;
     if (fast) {
-        // kbin_run: edges + the two z compensation tables always live
-        // in LDS; the histograms do when they fit
-        const size_t tab = ((size_t)nx_edges + nmu_edges + 2 * A.d2)
-                           * sizeof(double);
         const size_t full = (size_t)NB * nfields * sizeof(double) + tab;
-        if (full <= 160 * 1024) {
+        if (full <= NBK_BIN_LDS_BUDGET) {
             static size_t raised = 0;
             if (full > 64 * 1024 && full > raised) {
                 (void)hipFuncSetAttribute(
@@ -681,7 +697,7 @@ static int launch_bin(const double* d1, const double* d2, BinArgs& A,
                                dim3(1024), tab, s, d1, d2, A, kedges,
                                muedges, xsum);
         }
-    } else if (lds_bytes <= 160 * 1024) {
+    } else if (lds_bytes <= NBK_BIN_LDS_BUDGET) {
         static size_t raised = 0;
         if (lds_bytes > 64 * 1024 && lds_bytes > raised) {
             (void)hipFuncSetAttribute(

@@ -304,6 +304,13 @@ int check_len(int64_t n, const char* who) {
 #define NBK_MAX_ELL 8
 #endif
 
+// LDS the kernel declares statically (per-column constants of the two
+// pipeline stages, 2152 B with the interlace phases), kept out of the
+// dynamic budget: a launch whose static + dynamic LDS exceeds the CU's
+// 160 KiB is invalid and aborts the queue.  _xbin_lds_fits in
+// algorithms/fftpower.py mirrors this number.
+#define NBK_XBIN_STATIC_LDS 4096
+
 struct XBinArgs {
     int64_t n0, n1, n2;        // global REAL mesh dims
     int64_t nzh;               // n2/2 + 1
@@ -417,6 +424,13 @@ __global__ void kxfft_bin(const double* __restrict__ data,
                       ckzl[2][16], ccy[2][16], ccz[2][16], cph[2][32];
     __shared__ unsigned char cw2[2][16], czl[2][16], cskip[2][16];
     __shared__ int s_nlive[2];
+    // these static arrays share the CU's 160 KiB with the dynamic
+    // allocation: the launcher budgets NBK_XBIN_STATIC_LDS for them
+    // (any further __shared__ array of this kernel must be added here)
+    static_assert(6 * sizeof(double[2][16]) + sizeof(double[2][32])
+                  + 3 * sizeof(unsigned char[2][16]) + sizeof(int[2])
+                  <= NBK_XBIN_STATIC_LDS,
+                  "kxfft_bin: static LDS above the launcher's reserve");
 
     const bool comp_on = A.win1 >= 0;
     for (int i = t; i < NB * nfields; i += T) h[i] = 0.0;
@@ -861,8 +875,9 @@ extern "C" int nbk_fft_x_bin_f64(const double* data, const double* data2,
     const size_t fixed_il = fixed
         + (il ? (size_t)nmesh[0] * sizeof(cdouble) : 0);
     const int nbufs = il ? 2 : 1;
+    const size_t lds_budget = 160 * 1024 - NBK_XBIN_STATIC_LDS;
     while (TI > 1 && fixed_il + (size_t)nbufs * nmesh[0] * (TI + 1)
-                         * sizeof(cdouble) > 160 * 1024)
+                         * sizeof(cdouble) > lds_budget)
         TI >>= 1;
     if ((int64_t)nmesh[0] * TI > regcap) {
         NBK_SET_ERR("nbk_fft_x_bin_f64: n0 too large for the register "
@@ -871,7 +886,7 @@ extern "C" int nbk_fft_x_bin_f64(const double* data, const double* data2,
     }
     const size_t shmem = fixed_il
         + (size_t)nbufs * nmesh[0] * (TI + 1) * sizeof(cdouble);
-    if (shmem > 160 * 1024) {
+    if (shmem > lds_budget) {
         NBK_SET_ERR("nbk_fft_x_bin_f64: LDS budget exceeded "
                     "(%zu B) — use the unfused path", shmem);
         return NBK_ERR_UNSUPPORTED;
