@@ -606,6 +606,54 @@ int nbk_fof_link_f64(const double* pos_soa, const int* fine_start, int64_t n,
 int nbk_fof_flatten_i32(const int* parent, int64_t n, int* root, int* err,
                         void* stream);
 
+/* k-th nearest neighbour ------------------------------------------------
+ * The replacement for cKDTree.query under nbodykit/algorithms/kdtree.py
+ * (KDDensity).  nbk_knn_max_k() is the largest k, 16.
+ *
+ * Input: the output of nbk_fof_fine_sort_f64, unchanged: the cell-sorted SoA
+ * planes pos_soa[3n], sindex[n] (the input index of every sorted slot) and
+ * fine_start[ncells + 1], in the block-major cell order of the grid
+ * (origin, inv_cell, ncoarse, fine) above.  inv_cell[a] = 0 is a flat axis
+ * (every particle in cell 0 of it).
+ *
+ * Output, in INPUT order: for the particle in sorted slot i,
+ * r2_out[sindex[i]] is the squared distance to its k-th nearest OTHER
+ * particle (every sorted slot j != i; coincident points are neighbours at
+ * distance 0) and index_out[sindex[i]] that particle's input index.  With
+ * fewer than k other particles: +inf and -1.  A slot whose sindex[i] lies
+ * outside [0, n) is skipped, never stored through.
+ *
+ * Distance: per axis d = x_i - x_j and d2 = d*d, or, periodic, the smallest
+ * of d*d, (d - L)*(d - L), (d + L)*(d + L) (positions wrapped into [0, L)
+ * by the caller; box is not read when periodic = 0);
+ * r2 = (dx2 + dy2) + dz2, every operation rounded separately.  Candidates
+ * are ordered by the pair (r2, input index), so both outputs are bitwise
+ * reproducible whatever the order inside a cell, ties included.
+ *
+ * Search: one thread per sorted particle visits the cells around its own
+ * ring by ring.  Ring s covers, per axis of n_a cells around cell c, the
+ * offsets [-min(s, (n_a-1)/2), min(s, n_a/2)] when periodic and
+ * [max(-s, -c), min(s, n_a-1-c)] otherwise, less the box of ring s - 1:
+ * no cell is visited twice.  It stops when every axis is covered, or when
+ * the k-th best r2 <= b*b, b the smallest distance from the particle to a
+ * face of the visited box on an axis not yet covered (faces on the edge of a
+ * non-periodic domain excluded), less 1e-9 cell sides, clamped at 0.  A
+ * cell of a ring whose nearest point, with the same guard, lies beyond the
+ * k-th best so far is not read.  Every
+ * loop bound is a function of (s, n_a, c); cell ranges are clamped to
+ * [0, n); no atomics, no waiting.  At most max n_a rings, so a thread reads
+ * at most ncells start-table entries.
+ *
+ * 1 <= k <= 16, 0 <= n < 2^31, a grid as above, finite origin and
+ * inv_cell >= 0, and box > 0 when periodic: anything else returns
+ * NBK_ERR_ARG with the outputs untouched.  n = 0 launches nothing. */
+int nbk_knn_max_k(void);
+int nbk_knn_f64(const double* pos_soa, const int* fine_start,
+                const int* sindex, int64_t n, const double origin[3],
+                const double inv_cell[3], const int ncoarse[3],
+                const int fine[3], const double box[3], int periodic, int k,
+                double* r2_out, int* index_out, void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

@@ -8,3 +8,4 @@ from .pair_counters import SimulationBoxPairCount, SurveyDataPairCount
 from .paircount_tpcf import SimulationBox2PCF, SurveyData2PCF
 from .threeptcf import SimulationBox3PCF, SurveyData3PCF
 from .fof import FOF
+from .kdtree import KDDensity

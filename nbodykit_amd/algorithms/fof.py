@@ -47,12 +47,13 @@ def cells_along(length, side):
     return n
 
 
-def fof_grid(periodic, box, ll, n, lo=None, hi=None):
+def fof_grid(periodic, box, ll, n, lo=None, hi=None, per_cell=2.):
     """(origin, inv_cell, ncoarse, fine) of the two-level grid: over
     [0, L) for a periodic run, over the bounding box [lo, hi] otherwise.
 
-    The cell side is max(ll, (2 V / n)^(1/3)), about two particles per
-    cell; per axis ncell = ncoarse * fine with fine = ceil(ncell / 34),
+    The cell side is max(ll, (per_cell V / n)^(1/3)), about ``per_cell``
+    particles per cell (FOF's two unless told otherwise); per axis
+    ncell = ncoarse * fine with fine = ceil(ncell / 34),
     rounded down to a multiple of fine, so sides only grow and never fall
     below ``ll``.  A flat axis gets one cell."""
     if periodic:
@@ -62,7 +63,7 @@ def fof_grid(periodic, box, ll, n, lo=None, hi=None):
         origin = numpy.asarray(lo, dtype='f8')
         extent = numpy.asarray(hi, dtype='f8') - origin
     volume = float(numpy.prod(extent))
-    side = max(float(ll), (2. * volume / max(int(n), 1)) ** (1. / 3))
+    side = max(float(ll), (per_cell * volume / max(int(n), 1)) ** (1. / 3))
     while True:
         ncell = [cells_along(e, side) for e in extent]
         fine = [-(-c // LEVEL_CELLS_PER_AXIS) for c in ncell]
@@ -112,37 +113,28 @@ def candidate_pairs(fine_start, ncoarse, fine, periodic):
 
 # ---- the device pipeline -----------------------------------------------
 
-def fof_minid(pos, ll, box, periodic, info=None):
+def two_level_sort(pos, grid, stage='fof'):
     """
-    ``minid`` of device positions: an int64 CUDA tensor that gives every
-    particle, in input order, the smallest input index of its group.
-
-    pos: (n, 3) f64 CUDA rows, already wrapped into the box for a periodic
-    run.  ``info``, if a dict, receives the grid and the start table.
+    The coarse sort and the fine pass of device positions over a grid of
+    :func:`fof_grid`: (spos, sindex, fine_start), the cell-sorted SoA
+    planes [3n] f64, the input index of every sorted slot [n] int32 and
+    the fine start table [ncells + 1] int32, in block-major cell order.
+    The two profiling stages are named ``<stage>_coarse_sort`` and
+    ``<stage>_fine_sort``.  pos: (n, 3) f64 CUDA rows, n > 0.
     """
     import torch
     from .pair_counters import kernel
     lib = hiplib.require()
     n = int(pos.shape[0])
     dev = torch.device('cuda')
-    if n == 0:
-        return torch.empty(0, dtype=torch.int64, device=dev)
-
-    lo = hi = None
-    if not periodic:
-        lo, hi = pos.amin(dim=0).tolist(), pos.amax(dim=0).tolist()
-    origin, inv_cell, ncoarse, fine = fof_grid(periodic, box, ll, n, lo, hi)
+    origin, inv_cell, ncoarse, fine = grid
     ncoarse_all = int(numpy.prod(ncoarse))
     ncells = ncoarse_all * int(numpy.prod(fine))
-
     stream = hiplib.cur_stream()
-    origin_c = hiplib.f64_arr(origin)
-    inv_c = hiplib.f64_arr(inv_cell)
-    ncoarse_c = hiplib.int_arr(ncoarse)
-    fine_c = hiplib.int_arr(fine)
-    grid_c = (origin_c, inv_c, ncoarse_c, fine_c)
+    grid_c = (hiplib.f64_arr(origin), hiplib.f64_arr(inv_cell),
+              hiplib.int_arr(ncoarse), hiplib.int_arr(fine))
 
-    with profiling.collect('fof_coarse_sort', units=n):
+    with profiling.collect(stage + '_coarse_sort', units=n):
         index = torch.arange(n, dtype=torch.float64, device=dev)
         chunk = kernel._sort_chunk(n, ncoarse_all)
         nchunks = -(-n // chunk)
@@ -160,7 +152,7 @@ def fof_minid(pos, ll, box, periodic, info=None):
             hiplib.dptr(bases), hiplib.dptr(cpos), hiplib.dptr(cindex),
             stream), 'nbk_fof_cell_scatter_f64')
 
-    with profiling.collect('fof_fine_sort', units=n):
+    with profiling.collect(stage + '_fine_sort', units=n):
         spos = torch.empty(3 * n, dtype=torch.float64, device=dev)
         sindex = torch.empty(n, dtype=torch.int32, device=dev)
         fine_start = torch.empty(ncells + 1, dtype=torch.int32, device=dev)
@@ -169,7 +161,33 @@ def fof_minid(pos, ll, box, periodic, info=None):
             hiplib.dptr(coarse_start), hiplib.dptr(spos),
             hiplib.dptr(sindex), hiplib.dptr(fine_start), stream),
             'nbk_fof_fine_sort_f64')
-    del cpos, cindex, mat, bases
+    return spos, sindex, fine_start
+
+
+def fof_minid(pos, ll, box, periodic, info=None):
+    """
+    ``minid`` of device positions: an int64 CUDA tensor that gives every
+    particle, in input order, the smallest input index of its group.
+
+    pos: (n, 3) f64 CUDA rows, already wrapped into the box for a periodic
+    run.  ``info``, if a dict, receives the grid and the start table.
+    """
+    import torch
+    lib = hiplib.require()
+    n = int(pos.shape[0])
+    dev = torch.device('cuda')
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+
+    lo = hi = None
+    if not periodic:
+        lo, hi = pos.amin(dim=0).tolist(), pos.amax(dim=0).tolist()
+    origin, inv_cell, ncoarse, fine = fof_grid(periodic, box, ll, n, lo, hi)
+    stream = hiplib.cur_stream()
+    ncoarse_c = hiplib.int_arr(ncoarse)
+    fine_c = hiplib.int_arr(fine)
+    spos, sindex, fine_start = two_level_sort(
+        pos, (origin, inv_cell, ncoarse, fine))
 
     parent = torch.arange(n, dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -2,7 +2,8 @@
 // union-find: the replacement for kdcount.cluster.fof under the
 // reference's nbodykit/algorithms/fof.py, f64 throughout.
 //
-// Cell grid: ncell[a] = ncoarse[a] * fine[a] cells per axis.  The fine
+// Cell grid (nbk_twolevel.h, shared with nbk_knn.hip):
+// ncell[a] = ncoarse[a] * fine[a] cells per axis.  The fine
 // cell of a particle is cell_axis() (nbk_cells.h); its coarse cell is
 // that INTEGER divided by fine[a] — never a second floor with a coarse
 // inv_cell, whose rounding could disagree with the first at a cell face.
@@ -44,37 +45,11 @@
 // memory side).  A stale load is harmless: an old parent is still an
 // ancestor, a stale "root" fails its CAS and returns the fresh value, and
 // two finds that meet in one node prove the particles connected already.
-#include "nbk_countsort.h"
-#include "nbk_cells.h"
+#include "nbk_twolevel.h"
 
 namespace {
 
 constexpr int FOF_LINK_THREADS = 256;
-
-struct FofGrid {
-    double origin[3];
-    double inv_cell[3];
-    int ncoarse[3];
-    int fine[3];
-
-    // fine cell per axis -> (coarse id, sub id)
-    __device__ __forceinline__ void split(const int c[3], int* coarse,
-                                          int* sub) const {
-        *coarse = ((c[0] / fine[0]) * ncoarse[1] + c[1] / fine[1])
-                  * ncoarse[2] + c[2] / fine[2];
-        *sub = ((c[0] % fine[0]) * fine[1] + c[1] % fine[1]) * fine[2]
-               + c[2] % fine[2];
-    }
-
-    __device__ __forceinline__ void locate(double x, double y, double z,
-                                           int* coarse, int* sub) const {
-        const int c[3] = {
-            cell_axis(x, origin[0], inv_cell[0], ncoarse[0] * fine[0]),
-            cell_axis(y, origin[1], inv_cell[1], ncoarse[1] * fine[1]),
-            cell_axis(z, origin[2], inv_cell[2], ncoarse[2] * fine[2])};
-        split(c, coarse, sub);
-    }
-};
 
 // the coarse sort's key
 struct FofCoarseKey {
@@ -89,58 +64,6 @@ struct FofCoarseKey {
         return coarse;
     }
 };
-
-// grid checks of every entry point; `who` names it
-int fof_grid(const char* who, const int ncoarse[3], const int fine[3],
-             int64_t* ncoarse_all, int64_t* nfine)
-{
-    *ncoarse_all = 1;
-    *nfine = 1;
-    for (int i = 0; i < 3; i++) {
-        if (ncoarse[i] < 1 || fine[i] < 1) {
-            NBK_SET_ERR("%s: ncoarse[%d] = %d, fine[%d] = %d", who, i,
-                        ncoarse[i], i, fine[i]);
-            return NBK_ERR_ARG;
-        }
-        *ncoarse_all *= ncoarse[i];
-        *nfine *= fine[i];
-        if (*ncoarse_all > NBK_SORT_LDS_INTS || *nfine > NBK_SORT_LDS_INTS) {
-            NBK_SET_ERR("%s: more than %lld coarse cells or sub-cells, the "
-                        "LDS histogram", who, (long long)NBK_SORT_LDS_INTS);
-            return NBK_ERR_ARG;
-        }
-    }
-    if (*ncoarse_all * *nfine >= ((int64_t)1 << 31)) {
-        NBK_SET_ERR("%s: %lld cells, needs fewer than 2^31", who,
-                    (long long)(*ncoarse_all * *nfine));
-        return NBK_ERR_ARG;
-    }
-    return NBK_OK;
-}
-
-int fof_key(const char* who, const double origin[3],
-            const double inv_cell[3], const int ncoarse[3],
-            const int fine[3], FofGrid* g, int64_t* ncoarse_all,
-            int64_t* nfine)
-{
-    const int rc = fof_grid(who, ncoarse, fine, ncoarse_all, nfine);
-    if (rc != NBK_OK) return rc;
-    for (int i = 0; i < 3; i++) {
-        g->origin[i] = origin[i];
-        g->inv_cell[i] = inv_cell[i];
-        g->ncoarse[i] = ncoarse[i];
-        g->fine[i] = fine[i];
-    }
-    return NBK_OK;
-}
-
-int fof_check_n(const char* who, int64_t n) {
-    if (n < 0 || n >= ((int64_t)1 << 31)) {
-        NBK_SET_ERR("%s: n=%lld (needs 0 <= n < 2^31)", who, (long long)n);
-        return NBK_ERR_ARG;
-    }
-    return NBK_OK;
-}
 
 // ---- fine pass ---------------------------------------------------------
 

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     'nbk_3pcf_max_ell', 'nbk_3pcf_max_bins', 'nbk_3pcf_zeta_f64',
     'nbk_fof_cell_count_f64', 'nbk_fof_cell_scatter_f64',
     'nbk_fof_fine_sort_f64', 'nbk_fof_link_f64', 'nbk_fof_flatten_i32',
+    'nbk_knn_max_k', 'nbk_knn_f64',
 ]
 
 _lib = None
@@ -223,6 +224,13 @@ def _declare(lib):
     lib.nbk_fof_flatten_i32.restype = ctypes.c_int
     lib.nbk_fof_flatten_i32.argtypes = [c_void, c_i64, c_void, c_void,
                                         c_void]
+    lib.nbk_knn_max_k.restype = ctypes.c_int
+    lib.nbk_knn_max_k.argtypes = []
+    lib.nbk_knn_f64.restype = ctypes.c_int
+    lib.nbk_knn_f64.argtypes = [c_void, c_void, c_void, c_i64, c_f64_p,
+                                c_f64_p, c_int_p, c_int_p, c_f64_p,
+                                ctypes.c_int, ctypes.c_int, c_void, c_void,
+                                c_void]
 
 
 def load():
