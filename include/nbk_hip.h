@@ -654,6 +654,82 @@ int nbk_knn_f64(const double* pos_soa, const int* fine_start,
                 const int fine[3], const double box[3], int periodic, int k,
                 double* r2_out, int* index_out, void* stream);
 
+/* cylindrical groups ----------------------------------------------------
+ * The replacement for the pair enumeration and the pandas groupby under
+ * nbodykit/algorithms/cgm.py (CylindricalGroups).
+ *
+ * Input: the output of nbk_fof_fine_sort_f64, unchanged (pos_soa[3n] and
+ * fine_start[ncells + 1] on the grid (ncoarse, fine) of the friends-of-
+ * friends block above, with its limits), and prio[n], the priority of every
+ * sorted slot: a permutation of 0..n-1, a higher value is a higher
+ * priority.  The caller guarantees distinct values; they are not checked.
+ * Everything written is in sorted-slot order.
+ *
+ * Neighbours: slots i and j are neighbours iff, with d = p_i - p_j per axis
+ * and, periodic, `if (d > box/2) d -= box; if (d <= -box/2) d += box;`
+ * (positions wrapped into [0, box) by the caller; box is not read when
+ * periodic = 0),
+ *   los_mode 0: rlos = (dx*los[0] + dy*los[1]) + dz*los[2],
+ *               rlos2 = rlos*rlos
+ *   los_mode 1 (observer at the origin; los is not read):
+ *               c = 0.5*(p_i + p_j), dot = (dx*cx + dy*cy) + dz*cz,
+ *               rlos2 = (dot*dot) / ((cx*cx + cy*cy) + cz*cz)
+ *   rsky2 = |((dx*dx + dy*dy) + dz*dz) - rlos2|
+ *   rsky2 <= rperp2 && rlos2 <= rpar2,
+ * every operation rounded separately; 0/0 is NaN and compares false (two
+ * objects placed symmetrically about the observer are not neighbours).
+ * The pair is tested from p_i - p_j under this wrap, never under a per-cell
+ * image shift.  The caller picks cells whose side on every axis covers the
+ * cylinder, so that a neighbour lies at most one cell away.
+ *
+ * Walk, common to the three calls: one thread per sorted slot visits every
+ * neighbour cell once: per axis of n_a cells the offsets
+ * [-min(1, (n_a-1)/2), min(1, n_a/2)] when periodic, [-1, 1] clamped to the
+ * grid otherwise.  Loop bounds are functions of the start table, clamped to
+ * [0, n]; no global read-modify-write, no waiting.
+ *
+ * nbk_cgm_resolve_f64: one sweep of the greedy selection over state[n]
+ * (zeroed by the caller; 0 undecided, 1 central, 2 satellite).  An
+ * undecided slot becomes a satellite if a neighbour of higher priority is a
+ * central, else a central if no neighbour of higher priority is undecided,
+ * else it stays.  `state` is read and written with agent-scope relaxed
+ * atomic loads and stores; a stale "undecided" only delays a decision, so
+ * the fixpoint, reached after at most n sweeps, is the sequential
+ * highest-priority-first selection whatever the thread order.  flags[2]
+ * (device ints, zeroed by the caller): flags[0] = 1 when the sweep decided
+ * something, flags[1] = 1 when a slot is still undecided after it, both
+ * plain stores.  A decided slot costs one load; a sweep over a final state
+ * writes nothing.
+ *
+ * nbk_cgm_host_f64 (state final): host[i] = i for a central, the slot of
+ * the highest-priority central among its neighbours for a satellite.
+ *
+ * nbk_cgm_count_f64: nsat[i] = the number of slots j != i in the neighbour
+ * cells of a central i with host[j] == i (no geometry, no atomics); 0 for a
+ * satellite.
+ *
+ * rperp2, rpar2 finite and >= 0, los_mode 0 or 1, los finite in mode 0,
+ * box > 0 and finite when periodic, 0 <= n < 2^31 and a grid within the
+ * limits above: anything else returns NBK_ERR_ARG with the outputs
+ * untouched.  n = 0 launches nothing. */
+int nbk_cgm_resolve_f64(const double* pos_soa, const int* fine_start,
+                        const int* prio, int64_t n, const int ncoarse[3],
+                        const int fine[3], const double box[3], int periodic,
+                        int los_mode, const double los[3], double rperp2,
+                        double rpar2, int* state, int* flags, void* stream);
+int nbk_cgm_host_f64(const double* pos_soa, const int* fine_start,
+                     const int* prio, int64_t n, const int ncoarse[3],
+                     const int fine[3], const double box[3], int periodic,
+                     int los_mode, const double los[3], double rperp2,
+                     double rpar2, const int* state, int* host,
+                     void* stream);
+int nbk_cgm_count_f64(const double* pos_soa, const int* fine_start,
+                      const int* prio, int64_t n, const int ncoarse[3],
+                      const int fine[3], const double box[3], int periodic,
+                      int los_mode, const double los[3], double rperp2,
+                      double rpar2, const int* state, const int* host,
+                      int* nsat, void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

@@ -9,3 +9,4 @@ from .paircount_tpcf import SimulationBox2PCF, SurveyData2PCF
 from .threeptcf import SimulationBox3PCF, SurveyData3PCF
 from .fof import FOF
 from .kdtree import KDDensity
+from .cgm import CylindricalGroups

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     'nbk_fof_cell_count_f64', 'nbk_fof_cell_scatter_f64',
     'nbk_fof_fine_sort_f64', 'nbk_fof_link_f64', 'nbk_fof_flatten_i32',
     'nbk_knn_max_k', 'nbk_knn_f64',
+    'nbk_cgm_resolve_f64', 'nbk_cgm_host_f64', 'nbk_cgm_count_f64',
 ]
 
 _lib = None
@@ -231,6 +232,17 @@ def _declare(lib):
                                 c_f64_p, c_int_p, c_int_p, c_f64_p,
                                 ctypes.c_int, ctypes.c_int, c_void, c_void,
                                 c_void]
+    # (pos, start, prio, n, ncoarse, fine, box, periodic, los_mode, los,
+    # rperp2, rpar2), then the visitor's arrays and the stream
+    cgm_common = [c_void, c_void, c_void, c_i64, c_int_p, c_int_p, c_f64_p,
+                  ctypes.c_int, ctypes.c_int, c_f64_p, c_f64, c_f64]
+    lib.nbk_cgm_resolve_f64.restype = ctypes.c_int
+    lib.nbk_cgm_resolve_f64.argtypes = cgm_common + [c_void, c_void, c_void]
+    lib.nbk_cgm_host_f64.restype = ctypes.c_int
+    lib.nbk_cgm_host_f64.argtypes = cgm_common + [c_void, c_void, c_void]
+    lib.nbk_cgm_count_f64.restype = ctypes.c_int
+    lib.nbk_cgm_count_f64.argtypes = cgm_common + [c_void, c_void, c_void,
+                                                   c_void]
 
 
 def load():

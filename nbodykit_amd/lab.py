@@ -35,6 +35,7 @@ from nbodykit_amd.algorithms.paircount_tpcf import (SimulationBox2PCF,
 from nbodykit_amd.algorithms import SimulationBox3PCF, SurveyData3PCF
 from nbodykit_amd.algorithms import FOF
 from nbodykit_amd.algorithms import KDDensity
+from nbodykit_amd.algorithms import CylindricalGroups
 from nbodykit_amd import filters
 from nbodykit_amd.source.catalog.species import MultipleSpeciesCatalog
 from nbodykit_amd import io as IO
