@@ -730,6 +730,56 @@ int nbk_cgm_count_f64(const double* pos_soa, const int* fine_start,
                       double rpar2, const int* state, const int* host,
                       int* nsat, void* stream);
 
+/* fibre assignment -------------------------------------------------------
+ * The replacement for the loop over collision groups under
+ * nbodykit/algorithms/fibercollisions.py (FiberCollisions).
+ * nbk_fibers_max_group() is the largest group, 1024 members.
+ *
+ * Input: pos_aos[3n] (n rows of x, y, z), read only through midx;
+ * midx[nmember], the input indices of the members of every group, group
+ * after group and ascending inside a group; gstart[ngroup + 1], the start
+ * table into midx.  collided[nmember] and neighbor[nmember] are written in
+ * member order.  nbig is the caller's promise that no group at index >= nbig
+ * has more than 64 members.
+ *
+ * Members a and b collide iff, with d = p_a - p_b per axis,
+ * (dx*dx + dy*dy) + dz*dz <= r2, every operation rounded separately (the
+ * predicate of nbk_fof_link_f64).  Inside one group all members start
+ * active; per round, among the active members, n_coll[j] counts those
+ * colliding with j and n_other[j] sums n_coll over them.  When every n_coll
+ * is 0 the round loop ends.  Otherwise one member is marked collided and
+ * deactivated: largest n_coll, then smallest n_other, then smallest key,
+ * then smallest position inside the group, with, modulo 2^64 and i the
+ * input index,
+ *   z = seed + (i + 1) * 0x9E3779B97F4A7C15
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   key = z ^ (z >> 31).
+ * collided is 1 for a marked member and 0 otherwise.  neighbor is, for a
+ * marked member, the input index of the unmarked member of its group with the
+ * smallest squared distance (ties to the earlier member), -1 otherwise.  A
+ * group is not assumed connected; one without a collision, and a group of
+ * one member, come out all 0 and -1.
+ *
+ * Two launches: one block per group [0, nbig) for the groups of more than 64
+ * members there, and one wave per group, four per block, for every group of
+ * up to 64 members.  No global atomics, nothing shared between blocks; start
+ * table entries are clamped to [0, nmember] and every loop is bounded by the
+ * clamped size.  *err (device int, zeroed by the caller) is set, and the
+ * group's outputs are left untouched, for a group above the cap, a group at
+ * or beyond nbig with more than 64 members, and a member index outside
+ * [0, n).
+ *
+ * r2 finite and >= 0, 0 <= n, nmember, ngroup < 2^31, 0 <= nbig <= ngroup and
+ * no null pointer with a non-zero count: anything else returns NBK_ERR_ARG
+ * with nothing written.  ngroup = 0 launches nothing. */
+int nbk_fibers_max_group(void);
+int nbk_fibers_assign_f64(const double* pos_aos, int64_t n, const int* midx,
+                          int64_t nmember, const int* gstart, int64_t ngroup,
+                          int64_t nbig, double r2, uint64_t seed,
+                          int* collided, int* neighbor, int* err,
+                          void* stream);
+
 /* small helpers ------------------------------------------------------ */
 /* out[i] += a[i]  (f64, n elements) */
 int nbk_axpy_f64(double* out, const double* a, double alpha, int64_t n,

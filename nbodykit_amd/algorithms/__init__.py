@@ -10,3 +10,4 @@ from .threeptcf import SimulationBox3PCF, SurveyData3PCF
 from .fof import FOF
 from .kdtree import KDDensity
 from .cgm import CylindricalGroups
+from .fibercollisions import FiberCollisions

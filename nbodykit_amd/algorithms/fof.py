@@ -164,13 +164,14 @@ def two_level_sort(pos, grid, stage='fof'):
     return spos, sindex, fine_start
 
 
-def fof_minid(pos, ll, box, periodic, info=None):
+def fof_minid(pos, ll, box, periodic, info=None, per_cell=2.):
     """
     ``minid`` of device positions: an int64 CUDA tensor that gives every
     particle, in input order, the smallest input index of its group.
 
     pos: (n, 3) f64 CUDA rows, already wrapped into the box for a periodic
     run.  ``info``, if a dict, receives the grid and the start table.
+    ``per_cell`` is fof_grid's: it changes the cells, never the result.
     """
     import torch
     lib = hiplib.require()
@@ -182,7 +183,8 @@ def fof_minid(pos, ll, box, periodic, info=None):
     lo = hi = None
     if not periodic:
         lo, hi = pos.amin(dim=0).tolist(), pos.amax(dim=0).tolist()
-    origin, inv_cell, ncoarse, fine = fof_grid(periodic, box, ll, n, lo, hi)
+    origin, inv_cell, ncoarse, fine = fof_grid(periodic, box, ll, n, lo, hi,
+                                               per_cell=float(per_cell))
     stream = hiplib.cur_stream()
     ncoarse_c = hiplib.int_arr(ncoarse)
     fine_c = hiplib.int_arr(fine)

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     'nbk_fof_fine_sort_f64', 'nbk_fof_link_f64', 'nbk_fof_flatten_i32',
     'nbk_knn_max_k', 'nbk_knn_f64',
     'nbk_cgm_resolve_f64', 'nbk_cgm_host_f64', 'nbk_cgm_count_f64',
+    'nbk_fibers_max_group', 'nbk_fibers_assign_f64',
 ]
 
 _lib = None
@@ -243,6 +244,13 @@ def _declare(lib):
     lib.nbk_cgm_count_f64.restype = ctypes.c_int
     lib.nbk_cgm_count_f64.argtypes = cgm_common + [c_void, c_void, c_void,
                                                    c_void]
+    lib.nbk_fibers_max_group.restype = ctypes.c_int
+    lib.nbk_fibers_max_group.argtypes = []
+    lib.nbk_fibers_assign_f64.restype = ctypes.c_int
+    lib.nbk_fibers_assign_f64.argtypes = [c_void, c_i64, c_void, c_i64,
+                                          c_void, c_i64, c_i64, c_f64,
+                                          ctypes.c_uint64, c_void, c_void,
+                                          c_void, c_void]
 
 
 def load():

@@ -36,6 +36,7 @@ from nbodykit_amd.algorithms import SimulationBox3PCF, SurveyData3PCF
 from nbodykit_amd.algorithms import FOF
 from nbodykit_amd.algorithms import KDDensity
 from nbodykit_amd.algorithms import CylindricalGroups
+from nbodykit_amd.algorithms import FiberCollisions
 from nbodykit_amd import filters
 from nbodykit_amd.source.catalog.species import MultipleSpeciesCatalog
 from nbodykit_amd import io as IO
